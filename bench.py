@@ -7,7 +7,21 @@ per rank (8 coils x 20 frames x 192 x 160, 2 ESPIRiT maps, VDkt mask, seed
 L1 loss, backward, RCCL gradient all-reduce (N > 1), Adam step.  Inputs are
 resident in HBM before timing.  Weak scaling: one slice per rank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set up, W warmup steps, K
+timed steps in --dtype, the optional output dump, the JSON line.  --dump-outputs
+DIR writes what the last timed step computed (rank 0: the reconstruction `pred`,
+the `loss`, a fixed seeded sample of every gradient bucket) as DIR/<name>.npy,
+float32, at most 48 MB in all.  Inputs and weights are seeded and the headline's
+Adam runs at learning rate 0 (the full update kernel, weights unchanged: see
+main()), so `pred` and `loss` repeat bitwise from run to run and the gradients to
+the rounding of the backward's float atomics, and two builds run with the same
+arguments can be compared output for output.  --full adds everything else the
+line can carry, on weights trained at the config's rate: the phase in the other
+dtype, the DropPath all-branches phase, the BASELINE config 2 / 3 / 5 keys, PSNR
+and gradient accuracy against the CPU oracle and the measured CPU baseline (each
+still has its own --no-... switch).
 
 N > 1: under torchrun (`python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N`, RANK / WORLD_SIZE in the environment) each process is one
@@ -16,10 +30,10 @@ processes (before anything touches the GPU) with a 127.0.0.1 rendezvous, the way
 the reference's `Trainer(gpus=devices)` does (train_swin.py:253-261).  Either way
 the world size must equal --gpus, or the run exits non-zero.
 
-The headline runs in fp32 (the reference's own arithmetic); a second
-phase in bf16 (BASELINE config 2's dtype) follows in the same process and is
-reported under the "bf16" key.  Prints ONE JSON line on rank 0 (see the harness
-contract in DESIGN.md).
+The headline runs in fp32 (the reference's own arithmetic); under
+--full a second phase in bf16 (BASELINE config 2's dtype) follows in the same
+process and is reported under the "bf16" key.  Prints ONE JSON line on rank 0
+(see the harness contract in DESIGN.md).
 """
 import argparse
 import json
@@ -61,19 +75,25 @@ def parse():
     ap.add_argument("--unrolls", type=int, default=10)
     ap.add_argument("--dtype", default="fp32", choices=["bf16", "fp32"],
                     help="headline compute dtype (fp32 = the reference's own precision)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the other-dtype phase, the all-branches phase, the BASELINE "
+                         "config keys and the CPU-oracle legs (PSNR, gradient accuracy, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="skip the second phase in the other dtype (reported under its dtype key)")
+                    help="with --full: skip the second phase in the other dtype (reported under its dtype key)")
     ap.add_argument("--coils", type=int, default=8)
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--ny", type=int, default=192)
     ap.add_argument("--nx", type=int, default=160)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU-oracle legs (PSNR, gradient accuracy, CPU baseline)")
     ap.add_argument("--no-configs", dest="configs", action="store_false",
-                    help="skip the BASELINE config 2 / 3 / 5 keys (5-unroll bf16, Swin-GAN, DiT DDPM_X)")
+                    help="with --full: skip the BASELINE config 2 / 3 / 5 keys (5-unroll bf16, Swin-GAN, DiT DDPM_X)")
     ap.add_argument("--config-steps", type=int, default=5)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-all-branches", dest="all_branches", action="store_false",
-                    help="skip the DropPath all-branches phase (profiling runs: exactly warmup + steps train steps)")
+                    help="with --full: skip the DropPath all-branches phase")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / timing plumbing only, on the CPU with gloo: each step all-reduces a "
                          "gradient-sized flat bucket (no HIP path; tests/test_bench_launch.py)")
@@ -645,6 +665,38 @@ def world_timing(elapsed, steps, world, dev):
     return max(per), [1000.0 * x / steps for x in per]
 
 
+DUMP_BUDGET_ELEMS = 12 << 20        # float32 elements in all dumped arrays together (48 MB; --dump-outputs)
+DUMP_GRAD_SAMPLE = 1 << 18          # elements kept of each gradient bucket
+
+
+def dump_outputs(path, loss, pred, buckets):
+    """--dump-outputs: what the last timed training step computed, as float32
+    <name>.npy under `path`: `pred` (the reconstruction, complex as a trailing
+    (re, im) axis; 9.8 MB at the BASELINE slice), `loss`, and the step's gradients
+    (after the all-reduce): per flat bucket of GradBuckets, one per unroll's network,
+    `grad_bucket<i>` holds DUMP_GRAD_SAMPLE of its elements -- 20 MB in all at the
+    BASELINE slice.  The arrays together stay within DUMP_BUDGET_ELEMS: if they would
+    not, the smallest are served first and each gets at most an equal share of what is
+    left.  An array that is cut keeps the elements at a seed-1000 random index set,
+    the same in every run."""
+    os.makedirs(path, exist_ok=True)
+    out = {"pred": (torch.view_as_real(pred.detach()), None), "loss": (loss.detach().reshape(1), None)}
+    flats = [f for f, _ in buckets.buckets] + ([buckets.extra[0]] if buckets.extra is not None else [])
+    for i, flat in enumerate(flats):
+        out[f"grad_bucket{i:02d}"] = (flat.detach(), DUMP_GRAD_SAMPLE)
+    want = {n: min(a.numel(), cap or a.numel()) for n, (a, cap) in out.items()}
+    left = DUMP_BUDGET_ELEMS
+    for k, n in enumerate(sorted(want, key=lambda n: (want[n], n))):
+        want[n] = min(want[n], left // (len(want) - k))
+        left -= want[n]
+    for name, (a, _) in out.items():
+        a = a.float().cpu().contiguous()
+        if want[name] < a.numel():
+            gen = torch.Generator().manual_seed(1000)
+            a = a.reshape(-1)[torch.randperm(a.numel(), generator=gen)[:want[name]].sort().values]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a.numpy(), dtype=np.float32))
+
+
 def dry_run(args, world, rank, backend):
     """--dry-run: the multi-rank plumbing of main() without the HIP path (CPU, gloo):
     W + K steps, each all-reducing a flat fp32 bucket, barrier-bracketed timing, max
@@ -728,7 +780,16 @@ def main():
     from dl_cs.mri import transforms as T
     A = T.SenseModel(data["maps"], weights=data["mask"])
     buckets = GradBuckets(model, world, collective=use_pg)
-    opt = optim.adam([p for p in model.parameters() if p.requires_grad], lr=cfg.OPTIMIZER.ADAM.LR)
+    # Adam at learning rate 0: every step runs the whole update (same fused kernel, same traffic:
+    # moments, bias correction, the write of p), but the weights stay at their seeded initialisation,
+    # so each step's forward starts from the same weights and the run's outputs repeat from run to run
+    # (the forward is run-to-run deterministic).  At cfg.OPTIMIZER.ADAM.LR they did not: the float
+    # atomics in the backward's small reductions (LayerNorm, bias and bias-table gradients) differ in
+    # the last bits between runs, and Adam's near-sign first updates turn that into 6e-4 of the
+    # reconstruction after 5 steps and 3 % after 25.  The backward still shows in --dump-outputs:
+    # the last step's gradients are dumped beside pred and loss.  --full restores the config's
+    # rate after the headline.
+    opt = optim.adam([p for p in model.parameters() if p.requires_grad], lr=0.0)
 
     def step():
         buckets.zero()
@@ -737,7 +798,10 @@ def main():
         loss.backward()
         buckets.finish()
         opt.step()
+        last["pred"], last["loss"] = pred.detach(), loss.detach()
         return loss
+
+    last = {}                                   # what the newest step handed back (--dump-outputs)
 
     def phase(dtype, steps, warmup):
         """W untimed + K timed training steps in one compute dtype; max over ranks."""
@@ -813,15 +877,26 @@ def main():
 
     head = phase(args.dtype, args.steps, args.warmup)
     log(f"{args.dtype} phase: {head['value']:.3f} slices/s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["loss"], last["pred"], buckets)
+    if args.full:
+        # the legs of --full run, as they always did, on weights with the benchmark's training
+        # history behind them: the config's rate from here on, and first the headline's W + K
+        # steps once more at that rate (untimed) -- the updates the headline itself left out
+        for g in opt.param_groups:
+            g["lr"] = cfg.OPTIMIZER.ADAM.LR
+        for _ in range(args.warmup + args.steps):
+            step()
+        torch.cuda.synchronize()
     other = "bf16" if args.dtype == "fp32" else "fp32"
-    sec = phase(other, args.steps, max(1, args.warmup)) if args.secondary else None
+    sec = phase(other, args.steps, max(1, args.warmup)) if args.full and args.secondary else None
     if sec is not None:
         log(f"{other} phase: {sec['value']:.3f} slices/s")
     # DropPath: the timed train step draws stochastic depth (p = 0 .. 0.2, vst:603) and a
     # dropped branch skips its forward GEMMs and its whole backward (its gradient is zero);
     # the reference's autograd still computes it.  Same step with every branch computed:
     full = None
-    if args.all_branches:
+    if args.full and args.all_branches:
         dps = [m for m in model.modules() if type(m).__name__ == "DropPath"]
         saved = [m.drop_prob for m in dps]
         for m in dps:
@@ -830,7 +905,7 @@ def main():
         for m, pr in zip(dps, saved):
             m.drop_prob = pr
     extra = {}
-    if args.configs and world == 1:
+    if args.full and args.configs and world == 1:
         extra["config2_bf16_5unroll"] = config2_phase(args, dev, data, args.config_steps)
         log("config 2 done")
         extra["config3_swin_gan"] = gan_phase(args, model, data, A, buckets, opt, args.config_steps)
@@ -861,7 +936,7 @@ def main():
             "config": {"workload": f"configs/config_swin.yaml, PGD {args.unrolls}-iter unroll, Swin regularizer, "
                                    f"1 cine slice per rank: {args.coils} coils x {args.frames} frames x "
                                    f"{args.ny} x {args.nx}, 2 ESPIRiT maps, train step (fwd+bwd+Adam)",
-                       "global_batch": world, "unrolls": args.unrolls,
+                       "global_batch": world, "unrolls": args.unrolls, "adam_lr": 0.0,
                        "parallelism": f"dp{world} (one slice per rank, RCCL grad all-reduce)"},
         }
         line.update({k: head[k] for k in ("per_rank_ms_per_step", "allreduce", "roofline", "roofline_conv",
@@ -881,7 +956,7 @@ def main():
                     (head["roofline_attention"] or {}).get("launches", 0) / args.steps,
             }
         line.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or cpu_threads()
             line["psnr_vs_ref"] = psnr_vs_oracle(model, data, args, threads, [args.dtype] + ([other] if sec else []))
             log("psnr_vs_ref done")

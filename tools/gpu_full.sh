@@ -9,6 +9,6 @@ timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout
 tail -2 $OUT/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo SMOKE_FAILED; tail -30 $OUT/smoke.log; exit 1; }
 cat $OUT/smoke.log
-timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1 || { echo BENCH_FAILED; tail -30 $OUT/bench.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1 || { echo BENCH_FAILED; tail -30 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log
 bash tools/profile_round.sh $TAG

@@ -16,5 +16,5 @@ for k in "conv3d_k3_v6_kernel<1,:fwd" "conv3d_k3_v6_kernel<4,:dgrad" "conv3d_wgr
   python3 tools/pmc_traffic.py "$(cc pmc_bf16_FETCH_SIZE)" "$(cc pmc_bf16_WRITE_SIZE)" "${k%%:*}" > $OUT/traffic_bf16_conv_${k##*:}.json
 done
 cat $OUT/traffic_*.json
-timeout -k 10 1100 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 1100 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -20 $OUT/bench.err; exit 1; }
 grep "^{" $OUT/bench.json | tail -1 | cut -c1-600

@@ -3,5 +3,5 @@
 set -o pipefail
 OUT=gpurun_out/r06gg
 mkdir -p $OUT
-timeout -k 10 1000 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 1000 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail -20 $OUT/bench.err; exit 1; }
 grep "^{" $OUT/bench.json | tail -1 | cut -c1-200
