@@ -8,7 +8,11 @@
 // The 2D FFT is split into an X-pass ("rows", X contiguous) and a Y-pass
 // ("cols", strided by X); each pass runs a mixed-radix (2,3,4,5) Stockham
 // autosort FFT on a batch of lines staged in LDS, twiddles from a per-block
-// double-precision table.  The coil combine (forward) and the conj-map coil
+// double-precision table.  Lengths with a factor 7, 11 or 13 add one Stockham
+// pass per such factor, every other length <= 1024 runs Bluestein's chirp-z on
+// the staged lines (sense_anylen.inc); each has kernels of its own (GEN 1, 2),
+// so the 2-3-5-smooth lengths keep the kernels they had.
+// The coil combine (forward) and the conj-map coil
 // reduction + PGD data-consistency epilogue (adjoint) are fused into the row
 // pass, the mask and the 1/sqrt(YX) scale into the column pass, so each op is
 // two launches and one k-space-sized intermediate (which stays in the 256 MiB
@@ -33,16 +37,46 @@ struct FftPlan {
     int radix[12];
 };
 
-static bool make_plan(int n, FftPlan& p) {
-    if (n < 1 || n > 1024) return false;
-    p.n = n;
-    p.npass = 0;
-    int m = n;
-    const int rs[4] = {4, 2, 3, 5};
-    for (int r : rs) {
+// What a length needs beyond its Stockham passes.  kind 0: 2-3-5-smooth, the
+// passes are {4, 2, 3, 5} only.  kind 1: passes of 7, 11 or 13 follow them.
+// kind 2 (Bluestein): a factor outside {2,3,5,7,11,13} remains; the line is
+// convolved with a chirp at the padded length m, the smallest 2-3-5-smooth
+// integer >= 2n - 1 (<= 2048), whose smooth plan is `inner`; the outer plan has
+// no pass.
+enum { kPlanSmooth = 0, kPlanMixed = 1, kPlanBluestein = 2 };
+struct FftAux {
+    int kind, m;
+    FftPlan inner;
+};
+
+static int factor_out(int m, FftPlan& p, const int* rs, int nr) {
+    for (int q = 0; q < nr; ++q) {
+        const int r = rs[q];
         while (m % r == 0) { p.radix[p.npass++] = r; m /= r; }
     }
-    return m == 1 && p.npass <= 12;
+    return m;
+}
+
+static bool make_plan(int n, FftPlan& p, FftAux& aux) {
+    if (n < 1 || n > 1024) return false;
+    const int smooth[4] = {4, 2, 3, 5}, odd[3] = {7, 11, 13};
+    p.n = n;
+    p.npass = 0;
+    aux.kind = kPlanSmooth;
+    aux.m = n;
+    aux.inner.n = n;
+    aux.inner.npass = 0;
+    int m = factor_out(n, p, smooth, 4);
+    if (m == 1) return true;
+    aux.kind = kPlanMixed;
+    if (factor_out(m, p, odd, 3) == 1) return true;
+    aux.kind = kPlanBluestein;
+    p.npass = 0;
+    for (int M = 2 * n - 1;; ++M) {
+        aux.inner.n = M;
+        aux.inner.npass = 0;
+        if (factor_out(M, aux.inner, smooth, 4) == 1) { aux.m = M; return true; }
+    }
 }
 
 DLCS_DEV float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -58,6 +92,9 @@ DLCS_DEV void build_twiddles(float2* tw, int n) {
         tw[m] = make_float2((float)c, (float)s);
     }
 }
+
+// R = 7, 11, 13 (sense_anylen.inc)
+template <int R> DLCS_DEV void dft_odd(float2 (&a)[R], bool inv);
 
 // in-register R-point DFT; inverse uses conjugate roots.
 template <int R>
@@ -103,6 +140,8 @@ DLCS_DEV void dft(float2 (&a)[R], bool inv) {
         a[4] = csub(m1, r1);
         a[2] = cadd(m2, r2);
         a[3] = csub(m2, r2);
+    } else {
+        dft_odd<R>(a, inv);
     }
 }
 
@@ -152,13 +191,25 @@ DLCS_DEV void stockham_pass(float2* buf, int si, int sb, int nbatch, int n, int 
     __syncthreads();
 }
 
-template <int MAXPTS>
+// GEN 0: the 2-3-5-smooth plans; GEN 1: also passes of 7, 11 and 13.
+template <int MAXPTS, int GEN = 0>
 DLCS_DEV void fft_lds(float2* buf, int si, int sb, int nbatch, const FftPlan& plan,
                       const float2* tw, bool inv) {
     const bool ifast = (si == 1);
     int p = 1;
     for (int q = 0; q < plan.npass; ++q) {
         const int r = plan.radix[q];
+        if constexpr (GEN == 1) {
+            if (r > 5) {
+                switch (r) {
+                    case 7: stockham_pass<7, MAXPTS>(buf, si, sb, nbatch, plan.n, p, tw, inv, ifast); break;
+                    case 11: stockham_pass<11, MAXPTS>(buf, si, sb, nbatch, plan.n, p, tw, inv, ifast); break;
+                    default: stockham_pass<13, MAXPTS>(buf, si, sb, nbatch, plan.n, p, tw, inv, ifast); break;
+                }
+                p *= r;
+                continue;
+            }
+        }
         switch (r) {
             case 2: stockham_pass<2, MAXPTS>(buf, si, sb, nbatch, plan.n, p, tw, inv, ifast); break;
             case 3: stockham_pass<3, MAXPTS>(buf, si, sb, nbatch, plan.n, p, tw, inv, ifast); break;
@@ -189,8 +240,38 @@ struct RowArgs {
     int dbg_nofft;         // timing experiments only (DLCS_SENSE_NOFFT=1): skip the FFT
 };
 
-template <int MODE>
-__global__ void __launch_bounds__(kThreads) sense_rows_kernel(RowArgs a) {
+// LDS of a Bluestein block (kind 2), behind its staged lines: the inner plan's
+// twiddles [m], the filter spectrum [m] and the padded lines [lines * m].  The
+// chirp [n] takes the place of the outer twiddle table, which has no pass to serve.
+struct BlueLds {
+    float2 *twm, *filt, *work;
+};
+
+// sense_anylen.inc.  blue_tables: the per-block tables of a GEN 2 kernel (chirp,
+// inner twiddles, filter spectrum), built once per block.
+// bluestein_lds: fft_lds for a kind-2 length, same buffer layout.
+template <int MAXPTS>
+DLCS_DEV void blue_tables(float2* chirp, float2* behind, int n, const FftAux& ax, bool inv, BlueLds& bl);
+template <int MAXPTS>
+DLCS_DEV void bluestein_lds(float2* buf, int si, int sb, int nbatch, int n, const FftAux& ax,
+                            const float2* chirp, const BlueLds& bl, bool inv);
+
+template <int MAXPTS, int GEN>
+DLCS_DEV void line_fft(float2* buf, int si, int sb, int nbatch, const FftPlan& plan, const float2* tw, bool inv,
+                       const FftAux* ax, const BlueLds& bl) {
+    if constexpr (GEN == 2) bluestein_lds<MAXPTS>(buf, si, sb, nbatch, plan.n, *ax, tw, bl, inv);
+    else fft_lds<MAXPTS, GEN>(buf, si, sb, nbatch, plan, tw, inv);
+}
+
+// The arguments of a GEN 2 kernel: the padded length and inner plan ride along.
+struct RowArgsBlue : RowArgs {
+    FftAux aux;
+};
+
+// GEN = the kind of X's plan.  0: 2-3-5-smooth; 1: with passes of 7, 11, 13
+// (both ARGS = RowArgs); 2: Bluestein (ARGS = RowArgsBlue).
+template <int MODE, int GEN = 0, typename ARGS = RowArgs>
+__global__ void __launch_bounds__(kThreads) sense_rows_kernel(ARGS a) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float2* tw = smem;                      // [X]
     float2* buf = smem + a.X;               // [rows * X]
@@ -199,14 +280,20 @@ __global__ void __launch_bounds__(kThreads) sense_rows_kernel(RowArgs a) {
     const int nrow = min(a.rows, Y - y0);
     const int npts = nrow * X;
     const int frame = blockIdx.y;           // MODE0: plane; else b*T + t
-    build_twiddles(tw, X);
+    if constexpr (GEN != 2) build_twiddles(tw, X);
     const bool inv = (MODE == 2) ? true : (MODE == 1 ? false : a.inverse != 0);
+    BlueLds bl{};
+    const FftAux* ax = nullptr;
+    if constexpr (GEN == 2) {
+        ax = &a.aux;
+        blue_tables<kRowPts>(tw, buf + a.rows * X, X, a.aux, inv, bl);
+    }
 
     if constexpr (MODE == 0) {
         const float2* src = a.in + ((size_t)frame * Y + y0) * X;
         for (int i = threadIdx.x; i < npts; i += kThreads) buf[i] = src[i];
         __syncthreads();
-        fft_lds<kRowPts>(buf, 1, X, nrow, a.plan, tw, inv);
+        line_fft<kRowPts, GEN>(buf, 1, X, nrow, a.plan, tw, inv, ax, bl);
         float2* dst = a.out + ((size_t)frame * Y + y0) * X;
         for (int i = threadIdx.x; i < npts; i += kThreads)
             dst[i] = make_float2(buf[i].x * a.scale, buf[i].y * a.scale);
@@ -241,7 +328,7 @@ __global__ void __launch_bounds__(kThreads) sense_rows_kernel(RowArgs a) {
                 }
             }
             __syncthreads();
-            fft_lds<kRowPts>(buf, 1, X, nrow, a.plan, tw, false);
+            line_fft<kRowPts, GEN>(buf, 1, X, nrow, a.plan, tw, false, ax, bl);
             float2* dst = a.out + ((((size_t)b * a.C + c) * a.T + t) * Y + y0) * X;
             for (int i = threadIdx.x; i < npts; i += kThreads) dst[i] = buf[i];
             __syncthreads();
@@ -257,7 +344,7 @@ __global__ void __launch_bounds__(kThreads) sense_rows_kernel(RowArgs a) {
             const float2* src = a.in + ((((size_t)b * a.C + c) * a.T + t) * Y + y0) * X;
             for (int i = threadIdx.x; i < npts; i += kThreads) buf[i] = src[i];
             __syncthreads();
-            fft_lds<kRowPts>(buf, 1, X, nrow, a.plan, tw, true);
+            line_fft<kRowPts, GEN>(buf, 1, X, nrow, a.plan, tw, true, ax, bl);
 #pragma unroll
             for (int k = 0; k < kRowPts; ++k) {
                 const int i = threadIdx.x + k * kThreads;
@@ -296,6 +383,7 @@ __global__ void __launch_bounds__(kThreads) sense_rows_kernel(RowArgs a) {
     }
 }
 
+
 // ---------------------------------------------------------------------------
 // Column pass (FFT along Y over `cols` consecutive columns of one plane).
 // pre-multiply by weights (adjoint) or post-multiply (forward), times scale.
@@ -313,7 +401,13 @@ struct ColArgs {
     FftPlan plan;
 };
 
-__global__ void __launch_bounds__(kThreads) sense_cols_kernel(ColArgs a) {
+struct ColArgsBlue : ColArgs {
+    FftAux aux;
+};
+
+// GEN = the kind of Y's plan, as in sense_rows_kernel.
+template <int GEN = 0, typename ARGS = ColArgs>
+__global__ void __launch_bounds__(kThreads) sense_cols_kernel(ARGS a) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float2* tw = smem;
     float2* buf = smem + a.Y;
@@ -322,7 +416,14 @@ __global__ void __launch_bounds__(kThreads) sense_cols_kernel(ColArgs a) {
     const int ncol = min(a.cols, X - x0);
     const int plane = blockIdx.y;           // (b*C + c)*T + t   (or generic plane)
     const int npts = ncol * Y;
-    build_twiddles(tw, Y);
+    BlueLds bl{};
+    const FftAux* ax = nullptr;
+    if constexpr (GEN == 2) {
+        ax = &a.aux;
+        blue_tables<kMaxPts>(tw, buf + a.cols * Y, Y, a.aux, a.inverse != 0, bl);
+    } else {
+        build_twiddles(tw, Y);
+    }
     const float* wrow = nullptr;
     if (a.weights) {
         const int t = plane % a.T;
@@ -342,7 +443,7 @@ __global__ void __launch_bounds__(kThreads) sense_cols_kernel(ColArgs a) {
         buf[y * ncol + j] = v;
     }
     __syncthreads();
-    fft_lds<kMaxPts>(buf, ncol, 1, ncol, a.plan, tw, a.inverse != 0);
+    line_fft<kMaxPts, GEN>(buf, ncol, 1, ncol, a.plan, tw, a.inverse != 0, ax, bl);
     float2* dst = a.out + (size_t)plane * Y * X;
     for (int i = threadIdx.x; i < npts; i += kThreads) {
         const int y = i / ncol, j = i % ncol;
@@ -362,6 +463,46 @@ static int sense_nofft() {
 
 static int rows_per_block(int X, int Y) { int r = kRowPoints / X; if (r < 1) r = 1; return r > Y ? Y : r; }
 static int cols_per_block(int X, int Y) { int c = kPoints / Y; if (c > 16) c = 16; if (c < 1) c = 1; return c > X ? X : c; }
+
+#include "sense_anylen.inc"
+
+// The generic row / column launch of one direction.  kind 0 launches what it
+// always did, kind 1 the GEN 1 kernel on the same grid and LDS, kind 2 the GEN 2
+// kernel with the lines per block and the LDS of blue_lines() / blue_lds_points().
+template <int MODE>
+static void launch_rows(RowArgs ra, const FftAux& ax, unsigned frames, hipStream_t st) {
+    if (ax.kind == kPlanBluestein) ra.rows = blue_lines(ra.X, ax.m, kRowPoints, ra.Y);
+    const dim3 g(cdiv(ra.Y, ra.rows), frames);
+    size_t sh = (size_t)(ra.X + ra.rows * ra.X) * sizeof(float2);
+    if (ax.kind == kPlanSmooth) {
+        hipLaunchKernelGGL(sense_rows_kernel<MODE>, g, dim3(kThreads), sh, st, ra);
+    } else if (ax.kind == kPlanMixed) {
+        hipLaunchKernelGGL((sense_rows_kernel<MODE, 1>), g, dim3(kThreads), sh, st, ra);
+    } else {
+        RowArgsBlue rb{};
+        static_cast<RowArgs&>(rb) = ra;
+        rb.aux = ax;
+        sh = blue_lds_points(ra.X, ax.m, ra.rows) * sizeof(float2);
+        hipLaunchKernelGGL((sense_rows_kernel<MODE, 2, RowArgsBlue>), g, dim3(kThreads), sh, st, rb);
+    }
+}
+
+static void launch_cols(ColArgs ca, const FftAux& ax, unsigned planes, hipStream_t st) {
+    if (ax.kind == kPlanBluestein) ca.cols = blue_lines(ca.Y, ax.m, kPoints, std::min(ca.X, 16));
+    const dim3 g(cdiv(ca.X, ca.cols), planes);
+    size_t sh = (size_t)(ca.Y + ca.cols * ca.Y) * sizeof(float2);
+    if (ax.kind == kPlanSmooth) {
+        hipLaunchKernelGGL(sense_cols_kernel<>, g, dim3(kThreads), sh, st, ca);
+    } else if (ax.kind == kPlanMixed) {
+        hipLaunchKernelGGL(sense_cols_kernel<1>, g, dim3(kThreads), sh, st, ca);
+    } else {
+        ColArgsBlue cb{};
+        static_cast<ColArgs&>(cb) = ca;
+        cb.aux = ax;
+        sh = blue_lds_points(ca.Y, ax.m, ca.cols) * sizeof(float2);
+        hipLaunchKernelGGL((sense_cols_kernel<2, ColArgsBlue>), g, dim3(kThreads), sh, st, cb);
+    }
+}
 
 }  // namespace
 
@@ -498,11 +639,21 @@ size_t dlcs_sense_workspace_bytes(int64_t B, int64_t C, int64_t T, int64_t Y, in
     return (size_t)(B * C * T * Y * X) * sizeof(float2);
 }
 
+int dlcs_fft_plan(int64_t n, int* kind, int* padded_len) {
+    FftPlan p;
+    FftAux ax;
+    if (n < 1 || n > 1024 || !make_plan((int)n, p, ax)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    if (kind) *kind = ax.kind;
+    if (padded_len) *padded_len = ax.m;
+    return DLCS_OK;
+}
+
 int dlcs_fft2(const void* in, void* out, int64_t nplanes, int64_t Y, int64_t X, int inverse,
               void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(in && out && nplanes > 0);
     FftPlan px, py;
-    if (!make_plan((int)X, px) || !make_plan((int)Y, py) || X > kRowPoints || Y > kPoints) return DLCS_ERR_UNSUPPORTED_SIZE;
+    FftAux ax, ay;
+    if (!make_plan((int)X, px, ax) || !make_plan((int)Y, py, ay)) return DLCS_ERR_UNSUPPORTED_SIZE;
     if (workspace_bytes < (size_t)(nplanes * Y * X) * sizeof(float2) || !workspace) return DLCS_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const float scale = 1.0f / sqrtf((float)(Y * X));
@@ -517,9 +668,7 @@ int dlcs_fft2(const void* in, void* out, int64_t nplanes, int64_t Y, int64_t X, 
                        : rows_fast<0, false>((int)X, ra, g, kFRowWaves * 64, st);
     }
     if (!done) {
-        dim3 g1(cdiv(Y, ra.rows), (unsigned)nplanes);
-        size_t sh1 = (size_t)(X + ra.rows * X) * sizeof(float2);
-        hipLaunchKernelGGL(sense_rows_kernel<0>, g1, dim3(kThreads), sh1, st, ra);
+        launch_rows<0>(ra, ax, (unsigned)nplanes, st);
     }
     ColArgs ca{};
     ca.in = (const float2*)workspace; ca.out = (float2*)out; ca.weights = nullptr; ca.wc = 1;
@@ -531,9 +680,7 @@ int dlcs_fft2(const void* in, void* out, int64_t nplanes, int64_t Y, int64_t X, 
         done = inverse ? cols_fast<true>((int)Y, ca, g, st) : cols_fast<false>((int)Y, ca, g, st);
     }
     if (!done) {
-        dim3 g2(cdiv(X, ca.cols), (unsigned)nplanes);
-        size_t sh2 = (size_t)(Y + ca.cols * Y) * sizeof(float2);
-        hipLaunchKernelGGL(sense_cols_kernel, g2, dim3(kThreads), sh2, st, ca);
+        launch_cols(ca, ay, (unsigned)nplanes, st);
     }
     return dlcs_launch_status();
 }
@@ -545,7 +692,8 @@ int dlcs_sense_fwd(const void* x, const void* maps, const float* weights, int64_
     if (E > kMaxE) return DLCS_ERR_UNSUPPORTED_SIZE;
     DLCS_CHECK_ARG(!weights || weights_coils == 1 || weights_coils == C);
     FftPlan px, py;
-    if (!make_plan((int)X, px) || !make_plan((int)Y, py) || X > kRowPoints || Y > kPoints) return DLCS_ERR_UNSUPPORTED_SIZE;
+    FftAux ax, ay;
+    if (!make_plan((int)X, px, ax) || !make_plan((int)Y, py, ay)) return DLCS_ERR_UNSUPPORTED_SIZE;
     if (!workspace || workspace_bytes < dlcs_sense_workspace_bytes(B, C, T, Y, X)) return DLCS_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     RowArgs ra{};
@@ -559,9 +707,7 @@ int dlcs_sense_fwd(const void* x, const void* maps, const float* weights, int64_
         done = rows_fast<1, false>((int)X, ra, dim3(cdiv(Y, kFLW), (unsigned)(B * T)), nw * 64, st);
     }
     if (!done) {
-        dim3 g1(cdiv(Y, ra.rows), (unsigned)(B * T));
-        size_t sh1 = (size_t)(X + ra.rows * X) * sizeof(float2);
-        hipLaunchKernelGGL(sense_rows_kernel<1>, g1, dim3(kThreads), sh1, st, ra);
+        launch_rows<1>(ra, ax, (unsigned)(B * T), st);
     }
     ColArgs ca{};
     ca.in = (const float2*)workspace; ca.out = (float2*)y; ca.weights = weights; ca.wc = (int)(weights ? weights_coils : 1);
@@ -571,9 +717,7 @@ int dlcs_sense_fwd(const void* x, const void* maps, const float* weights, int64_
     done = false;
     if (cols_fast_ok(Y, X)) done = cols_fast<false>((int)Y, ca, dim3((unsigned)(X / kFColW), (unsigned)(B * C * T)), st);
     if (!done) {
-        dim3 g2(cdiv(X, ca.cols), (unsigned)(B * C * T));
-        size_t sh2 = (size_t)(Y + ca.cols * Y) * sizeof(float2);
-        hipLaunchKernelGGL(sense_cols_kernel, g2, dim3(kThreads), sh2, st, ca);
+        launch_cols(ca, ay, (unsigned)(B * C * T), st);
     }
     return dlcs_launch_status();
 }
@@ -586,7 +730,8 @@ int dlcs_sense_adj(const void* y, const void* maps, const float* weights, int64_
     if (E > kMaxE) return DLCS_ERR_UNSUPPORTED_SIZE;
     DLCS_CHECK_ARG(!weights || weights_coils == 1 || weights_coils == C);
     FftPlan px, py;
-    if (!make_plan((int)X, px) || !make_plan((int)Y, py) || X > kRowPoints || Y > kPoints) return DLCS_ERR_UNSUPPORTED_SIZE;
+    FftAux ax, ay;
+    if (!make_plan((int)X, px, ax) || !make_plan((int)Y, py, ay)) return DLCS_ERR_UNSUPPORTED_SIZE;
     if (!workspace || workspace_bytes < dlcs_sense_workspace_bytes(B, C, T, Y, X)) return DLCS_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     ColArgs ca{};
@@ -596,9 +741,7 @@ int dlcs_sense_adj(const void* y, const void* maps, const float* weights, int64_
     bool done = false;
     if (cols_fast_ok(Y, X)) done = cols_fast<true>((int)Y, ca, dim3((unsigned)(X / kFColW), (unsigned)(B * C * T)), st);
     if (!done) {
-        dim3 g1(cdiv(X, ca.cols), (unsigned)(B * C * T));
-        size_t sh1 = (size_t)(Y + ca.cols * Y) * sizeof(float2);
-        hipLaunchKernelGGL(sense_cols_kernel, g1, dim3(kThreads), sh1, st, ca);
+        launch_cols(ca, ay, (unsigned)(B * C * T), st);
     }
     RowArgs ra{};
     ra.in = (const float2*)workspace; ra.maps = (const float2*)maps; ra.out = (float2*)out;
@@ -613,9 +756,7 @@ int dlcs_sense_adj(const void* y, const void* maps, const float* weights, int64_
         done = rows_fast<2, true>((int)X, ra, dim3(cdiv(Y, kFLW), (unsigned)(B * T)), nw * 64, st);
     }
     if (!done) {
-        dim3 g2(cdiv(Y, ra.rows), (unsigned)(B * T));
-        size_t sh2 = (size_t)(X + ra.rows * X) * sizeof(float2);
-        hipLaunchKernelGGL(sense_rows_kernel<2>, g2, dim3(kThreads), sh2, st, ra);
+        launch_rows<2>(ra, ax, (unsigned)(B * T), st);
     }
     return dlcs_launch_status();
 }
@@ -633,7 +774,8 @@ int dlcs_sense_normal(const void* x, const void* maps, const float* weights, int
     if (E > kMaxE) return DLCS_ERR_UNSUPPORTED_SIZE;
     DLCS_CHECK_ARG(!weights || weights_coils == 1 || weights_coils == C);
     FftPlan px, py;
-    if (!make_plan((int)X, px) || !make_plan((int)Y, py) || X > kRowPoints || Y > kPoints) return DLCS_ERR_UNSUPPORTED_SIZE;
+    FftAux ax, ay;
+    if (!make_plan((int)X, px, ax) || !make_plan((int)Y, py, ay)) return DLCS_ERR_UNSUPPORTED_SIZE;
     if (!workspace || workspace_bytes < dlcs_sense_workspace_bytes(B, C, T, Y, X)) return DLCS_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float2* k = (float2*)workspace;
@@ -649,9 +791,7 @@ int dlcs_sense_normal(const void* x, const void* maps, const float* weights, int
         done = rows_fast<1, false>((int)X, ra, dim3(cdiv(Y, kFLW), (unsigned)(B * T)), nw * 64, st);
     }
     if (!done) {
-        dim3 g1(cdiv(Y, ra.rows), (unsigned)(B * T));
-        size_t sh1 = (size_t)(X + ra.rows * X) * sizeof(float2);
-        hipLaunchKernelGGL(sense_rows_kernel<1>, g1, dim3(kThreads), sh1, st, ra);
+        launch_rows<1>(ra, ax, (unsigned)(B * T), st);
     }
     // column passes, in place on k
     ColArgs ca{};
@@ -662,12 +802,10 @@ int dlcs_sense_normal(const void* x, const void* maps, const float* weights, int
         ca.normal = 1; ca.inverse = 0; ca.weights_pre = 0; ca.scale = 1.0f / sqrtf((float)(Y * X));
         cols_fast<false>((int)Y, ca, dim3((unsigned)(X / kFColW), (unsigned)(B * C * T)), st);
     } else {
-        dim3 g2(cdiv(X, ca.cols), (unsigned)(B * C * T));
-        size_t sh2 = (size_t)(Y + ca.cols * Y) * sizeof(float2);
         ca.inverse = 0; ca.weights_pre = 0; ca.scale = 1.0f / sqrtf((float)(Y * X));
-        hipLaunchKernelGGL(sense_cols_kernel, g2, dim3(kThreads), sh2, st, ca);
+        launch_cols(ca, ay, (unsigned)(B * C * T), st);
         ca.inverse = 1; ca.weights_pre = 1; ca.scale = 1.0f;
-        hipLaunchKernelGGL(sense_cols_kernel, g2, dim3(kThreads), sh2, st, ca);
+        launch_cols(ca, ay, (unsigned)(B * C * T), st);
     }
     // adjoint row pass: IFFT_X, conj-map coil sum, epilogue
     RowArgs rb = ra;
@@ -680,9 +818,7 @@ int dlcs_sense_normal(const void* x, const void* maps, const float* weights, int
         done = rows_fast<2, true>((int)X, rb, dim3(cdiv(Y, kFLW), (unsigned)(B * T)), nw * 64, st);
     }
     if (!done) {
-        dim3 g2(cdiv(Y, rb.rows), (unsigned)(B * T));
-        size_t sh2 = (size_t)(X + rb.rows * X) * sizeof(float2);
-        hipLaunchKernelGGL(sense_rows_kernel<2>, g2, dim3(kThreads), sh2, st, rb);
+        launch_rows<2>(rb, ax, (unsigned)(B * T), st);
     }
     return dlcs_launch_status();
 }

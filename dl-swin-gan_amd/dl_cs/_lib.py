@@ -42,6 +42,7 @@ SIGNATURES = {
                                _SZ, _P],
     "dlcs_sense_cg_rows": [_P, _P, _P, _P, _I64, _P, _I64, _F, _INT, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P],
     "dlcs_fft2": [_P, _P, _I64, _I64, _I64, _INT, _P, _SZ, _P],
+    "dlcs_fft_plan": [_I64, _P, _P],
     "dlcs_window_index": [_I64] * 10 + [_P, _P, _P, _P],
     "dlcs_gather_rows": [_INT, _INT, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "dlcs_layernorm_fwd": [_INT, _P, _P, _P, _P, _F, _P, _P, _P, _I64, _I64, _P],

@@ -55,7 +55,10 @@ int dlcs_release_scratch(void);
  *   x       c64 [B,E,T,Y,X]      maps c64 [B,E,C,1,Y,X]
  *   weights f32 [B,Wc,T,Y,X] (Wc = 1 broadcast over coils, or C) or NULL
  *   y       c64 [B,C,T,Y,X]
- * Y and X must factor into 2,3,5 and be <= 1024.
+ * Any 1 <= Y, X <= 1024.  2-3-5-smooth lengths run Stockham passes of radix
+ * 4, 2, 3, 5; factors 7, 11 and 13 add one pass each; every other length runs
+ * Bluestein's algorithm on the same LDS-staged lines (dlcs_fft_plan tells
+ * which; DESIGN has what each costs).  Above 1024: DLCS_ERR_UNSUPPORTED_SIZE.
  * workspace: dlcs_sense_workspace_bytes() bytes (one k-space-sized buffer).
  * ------------------------------------------------------------------------- */
 size_t dlcs_sense_workspace_bytes(int64_t B, int64_t C, int64_t T, int64_t Y, int64_t X);
@@ -134,9 +137,18 @@ int dlcs_sense_cg_rows(void* x, const void* b, const void* maps, const float* we
                        void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
 
 /* Batched orthonormal 2D FFT over the last two dims of a c64 [nplanes,Y,X]
- * tensor (tr:31-46); in-place allowed.  Exposed for tests and FFT users.   */
+ * tensor (tr:31-46); in-place allowed.  Exposed for tests and FFT users.
+ * Any 1 <= Y, X <= 1024 (see dlcs_fft_plan); workspace: nplanes*Y*X c64.    */
 int dlcs_fft2(const void* in, void* out, int64_t nplanes, int64_t Y, int64_t X, int inverse,
               void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
+
+/* How dlcs_fft2 and the SENSE operators transform a line of n points (host
+ * only: no device, no launch).  *kind = 0: n is 2-3-5-smooth, Stockham passes of
+ * radix 4, 2, 3, 5; 1: passes of 7, 11 or 13 follow them; 2: another factor
+ * remains and the line goes through Bluestein's algorithm at *padded_len, the
+ * smallest 2-3-5-smooth integer >= 2n - 1.  *padded_len = n for kinds 0 and 1.
+ * Either pointer may be NULL.  DLCS_ERR_UNSUPPORTED_SIZE unless 1 <= n <= 1024. */
+int dlcs_fft_plan(int64_t n, int* kind, int* padded_len);
 
 
 /* ---------------------------------------------------------------------------
