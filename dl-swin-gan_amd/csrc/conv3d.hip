@@ -22,45 +22,36 @@
 #include "dlcs_common.h"
 
 #include <cstdlib>
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <type_traits>
 
 namespace {
 
-// Library-internal scratch (the producers' column-sum partials, the split-K / tail /
-// slab partials of the f16x3 kernels): one buffer per (slot, device, stream), grown on
-// demand and kept for the process (a stream's launches are ordered, so its buffers are
-// never shared with a concurrent launch on another stream).  Sizes at the BASELINE
-// slice, per stream: h3r split-K 69 MB, f16x3 weight-gradient slabs 88 MB, tail split
-// 42 MB, thin weight gradient 21 MB, column sums < 3 MB.  They bypass torch's caching
-// allocator: dlcs_scratch_bytes() reports them and dlcs_release_scratch() frees them
-// (after a device synchronisation) for a caller that needs the memory back.  Growing a
-// buffer synchronises its stream once (the old one may still be read); every size is
-// reached on the first step, so a steady step never grows one.
-enum ScratchSlot { kScrColsum, kScrH3r, kScrSplit2, kScrH3Tail, kScrWgH3, kScrTwp, kScrV6Tail, kScrBiasPart,
-                   kScrSlots };
-std::mutex g_scr_mu;
-std::map<std::tuple<int, int, hipStream_t>, std::pair<void*, size_t>> g_scr;
+// Caller workspaces (the producers' column-sum partials, the split-K / tail / slab
+// partials of the split kernels): each size decision below is one host function that
+// both the entry point's dlcs_*_workspace_bytes query and its launch call.  A size that
+// a per-launch test hook or a DIAG knob can change is the largest over its settings.
+inline size_t ws_align(size_t n) { return (n + 255) & ~(size_t)255; }          // sub-buffers at 256-B offsets
+inline bool ws_ok(const void* ws, size_t have, size_t need) { return need == 0 || (ws && have >= need); }
 
-void* scratch(int slot, hipStream_t st, size_t bytes) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_scr_mu);
-    auto& e = g_scr[{slot, dev, st}];
-    if (e.second < bytes) {
-        if (e.first) {
-            if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
-            (void)hipFree(e.first);
-        }
-        e.first = nullptr;
-        e.second = 0;
-        if (hipMalloc(&e.first, bytes) != hipSuccess) return nullptr;
-        e.second = bytes;
-    }
-    return e.first;
+// 4 x 8 x 8 output tiles (1 x 2 x 2 patches) of the 160-channel conv kernels
+inline long conv_tiles(long B, long D, long H, long W) { return B * (D / 4) * ((H / 4 + 1) / 2) * ((W / 4 + 1) / 2); }
+// tiles of the last partial round of 256 workgroups that run as 5 single-chunk
+// workgroups each (the tail split of the f16x3, v6 and v7 kernels), 0 = no split
+inline unsigned conv_tail_tiles(long ntile) {
+    const long ntail = ntile % 256;
+    return ntile > ntail && ntail > 0 && ntail * 5 <= 256 ? (unsigned)ntail : 0u;
 }
+// the tail split's partial tiles: [ntail][5][256][160] floats (v7: twice the units of 80 channels)
+inline size_t conv_tail_bytes(long ntile) { return (size_t)conv_tail_tiles(ntile) * 5 * 256 * 160 * sizeof(float); }
+
+// a weight gradient's voxel ranges: nr non-empty ranges of pp patches, nr <= want
+struct PatchRanges { int nr; long pp; };
+inline PatchRanges patch_ranges(long npatch, long want) {
+    const long n0 = std::max<long>(1, std::min<long>(want, npatch));
+    const long pp = (npatch + n0 - 1) / n0;
+    return {(int)((npatch + pp - 1) / std::max<long>(1, pp)), pp};
+}
+constexpr size_t kWgSlabBytes = (size_t)27 * 160 * 160 * sizeof(float);         // one range's dW partial
 
 constexpr int kHaloT = 6, kHaloY = 10, kHaloX = 10;
 constexpr int kHalo = kHaloT * kHaloY * kHaloX;     // 600 voxels
@@ -1685,8 +1676,15 @@ static bool conv_stamps_on() {
 template <typename T>
 size_t conv_smem(int nt) { return (size_t)(kHalo + 2 * nt * 32) * (CK + ConvPad<T>::v) * sizeof(T); }
 
+// the bf16 160 -> 160 forward / dgrad (v6, or v7 under its test hook) has a tail split
+inline size_t conv_k3_ws_bytes(int dtype, long cin, long cin_pad, long cout, long cout_pad, int relu_in, long B, long D,
+                               long H, long W) {
+    if (dtype != DLCS_BF16 || cin != 160 || cin_pad != 160 || cout != 160 || cout_pad != 160 || relu_in) return 0;
+    return conv_tail_bytes(conv_tiles(B, D, H, W));
+}
+
 template <typename T>
-int conv_launch(const ConvArgs& a, hipStream_t st) {
+int conv_launch(const ConvArgs& a, float* tail_ws, hipStream_t st) {
     const int nT = a.D / 4, nY = a.H / 4, nX = a.W / 4;
     const unsigned nblk = (unsigned)((long)a.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
     if constexpr (std::is_same<T, bf16>::value) {
@@ -1732,8 +1730,8 @@ int conv_launch(const ConvArgs& a, hipStream_t st) {
                 // v6; DLCS_CONV_V7=1 (test hook) runs the two-workgroups-per-CU v7 kernel
                 // (same-box A/B at parity: conv3d_v7.inc header, DESIGN round-6 item 1)
                 const char* f7 = dlcs_test_hook("DLCS_CONV_V7");
-                if (f7 && f7[0] == '1') return conv_v7_launch(v, st);
-                return conv_v6_launch(v, st);
+                if (f7 && f7[0] == '1') return conv_v7_launch(v, tail_ws, st);
+                return conv_v6_launch(v, tail_ws, st);
             } else {
                 // the two production epilogues (ResSwin / DFE tail forward: bf16 residual;
                 // dgrad: ReLU mask) and one runtime-flag variant for everything else
@@ -1796,11 +1794,24 @@ int conv_launch(const ConvArgs& a, hipStream_t st) {
     return dlcs_launch_status();
 }
 
+inline PatchRanges wg_c160_ranges(long npatch) { return patch_ranges(npatch, 28); }    // bf16 160 x 160
+inline PatchRanges wg_thin_ranges(long npatch) { return patch_ranges(npatch, 512); }   // bf16 thin ends
+
+// bf16 160 x 160: one slab per range; bf16 thin SFE with a bias gradient: one row of
+// 160 column sums per range; every other path (all of fp32): none
+inline size_t wgrad_k3_ws_bytes(int dtype, long cin, long cin_pad, long cout, long cout_pad, int relu_in, bool dbias,
+                                long npatch) {
+    if (dtype != DLCS_BF16 || relu_in || cout != 160 || cout_pad != 160) return 0;
+    if (cin == 160 && cin_pad == 160) return (size_t)wg_c160_ranges(npatch).nr * kWgSlabBytes;
+    if (cin <= 8 && dbias) return (size_t)wg_thin_ranges(npatch).nr * 160 * sizeof(float);
+    return 0;
+}
+
 template <typename T>
-int wgrad_launch(const WgradArgs& a, hipStream_t st, bool* bias_done);
+int wgrad_launch(const WgradArgs& a, float* ws, hipStream_t st, bool* bias_done);
 
 template <>
-int wgrad_launch<bf16>(const WgradArgs& a, hipStream_t st, bool* bias_done) {
+int wgrad_launch<bf16>(const WgradArgs& a, float* ws, hipStream_t st, bool* bias_done) {
     const int mt = a.cout_pad / 32, nt = a.cin_pad / 32;
     const long npatch = (long)a.B * (a.D / 4) * (a.H / 4) * (a.W / 4);
     int nrange = (int)(a.vox_per_block > 0 ? (npatch * 64 + a.vox_per_block - 1) / a.vox_per_block : 40);
@@ -1814,14 +1825,11 @@ int wgrad_launch<bf16>(const WgradArgs& a, hipStream_t st, bool* bias_done) {
         if ((2 * bias_rows + 128) * (std::max(a.cin_ld, a.g_ld) / 8) >= (1L << 26) || npatch >= (1L << 30) ||
             ((long)a.g_ld * 128 * 2) >= (1L << 31))
             return DLCS_ERR_UNSUPPORTED_SIZE;       // 32-bit lane offsets (16-B units << 6)
-        int nr = (int)std::min<long>(28, npatch);
-        const long pp = (npatch + nr - 1) / nr;
-        nr = (int)((npatch + pp - 1) / pp);
-        float* part = wgh3_workspace(st);           // the f16x3 weight gradient's slabs (same stream order)
-        if (!part) return (int)hipErrorOutOfMemory;
-        hipLaunchKernelGGL(conv3d_wgrad_c160_kernel, dim3((unsigned)(9 * nr)), dim3(768), 0, st, a, nr, (int)pp, part);
+        const PatchRanges r = wg_c160_ranges(npatch);
+        hipLaunchKernelGGL(conv3d_wgrad_c160_kernel, dim3((unsigned)(9 * r.nr)), dim3(768), 0, st, a, r.nr, (int)r.pp,
+                           ws);                     // one slab per range
         hipLaunchKernelGGL(wgrad_c160_reduce_kernel, dim3((unsigned)cdiv(27L * 160 * 40, 256)), dim3(256), 0, st,
-                           (const float*)part, a.dw, nr);
+                           (const float*)ws, a.dw, r.nr);
         return dlcs_launch_status();                // the bias (if asked) by the caller's column-sum pass
     }
     // thin ends (<= 8 channels on one side, 16-B rows there; 160 on the other)
@@ -1834,13 +1842,9 @@ int wgrad_launch<bf16>(const WgradArgs& a, hipStream_t st, bool* bias_done) {
         t.dw = a.dw; t.big_ld = thin_sfe ? a.g_ld : a.cin_ld; t.sgn = thin_sfe ? 1 : -1; t.big_is_co = thin_sfe;
         t.thin_ch = thin_sfe ? a.Cin : a.Cout; t.cout_pad = a.cout_pad; t.cin_pad = a.cin_pad;
         t.B = a.B; t.D = a.D; t.H = a.H; t.W = a.W;
-        int nr = (int)std::min<long>(512, npatch);
-        const int pp = (int)((npatch + nr - 1) / nr);
-        nr = (int)((npatch + pp - 1) / pp);            // every range non-empty (each writes its bias partial)
-        if (a.dbias && thin_sfe) {                     // the SFE bias gradient = column sums of g (the big side)
-            t.bpart = static_cast<float*>(scratch(kScrBiasPart, st, (size_t)nr * 160 * sizeof(float)));
-            if (!t.bpart) return (int)hipErrorOutOfMemory;
-        }
+        const PatchRanges r = wg_thin_ranges(npatch);      // every range non-empty (each writes its bias partial)
+        const int nr = r.nr, pp = (int)r.pp;
+        if (a.dbias && thin_sfe) t.bpart = ws;         // the SFE bias gradient = column sums of g (the big side)
         if (t.thin_ch <= 4)
             hipLaunchKernelGGL(conv3d_wgrad_thin_kernel<4>, dim3(nr), dim3(320), 0, st, t, nr, pp);
         else
@@ -1861,7 +1865,8 @@ int wgrad_launch<bf16>(const WgradArgs& a, hipStream_t st, bool* bias_done) {
 }
 
 template <>
-int wgrad_launch<float>(const WgradArgs& a, hipStream_t st, bool* bias_done) {
+int wgrad_launch<float>(const WgradArgs& a, float* ws, hipStream_t st, bool* bias_done) {
+    (void)ws;
     (void)bias_done;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (a.cout_pad == 160 && a.cin_pad == 160 && a.Cin == 160 && a.Cout == 160 && !a.relu_in && a.cin_ld % 4 == 0 &&
@@ -1909,32 +1914,6 @@ static unsigned grid_for(long n) {
 
 extern "C" {
 
-size_t dlcs_scratch_bytes(void) {
-    std::lock_guard<std::mutex> lk(g_scr_mu);
-    size_t n = 0;
-    for (const auto& e : g_scr) n += e.second.second;
-    return n;
-}
-
-int dlcs_release_scratch(void) {
-    std::lock_guard<std::mutex> lk(g_scr_mu);
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return dlcs_launch_status();
-    int st = 0;
-    std::map<int, bool> synced;
-    for (auto& e : g_scr) {
-        const int dev = std::get<1>(e.first);
-        if (!synced[dev]) {
-            synced[dev] = true;
-            if (hipSetDevice(dev) != hipSuccess || hipDeviceSynchronize() != hipSuccess) st = dlcs_launch_status();
-        }
-        if (e.second.first && hipFree(e.second.first) != hipSuccess && !st) st = dlcs_launch_status();
-    }
-    g_scr.clear();
-    (void)hipSetDevice(cur);
-    return st;
-}
-
 #ifdef DLCS_DIAG_BUILD
 int dlcs_debug_h3_stamps(void* host, int64_t n) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_h3_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
@@ -1945,14 +1924,22 @@ int dlcs_debug_conv_stamps(void* host, int64_t n) {
 }
 #endif
 
+size_t dlcs_conv3d_k3_workspace_bytes(int dtype, int64_t cin, int64_t cin_pad, int64_t cout, int64_t cout_pad,
+                                      int relu_in, int64_t B, int64_t D, int64_t H, int64_t W) {
+    return conv_k3_ws_bytes(dtype, cin, cin_pad, cout, cout_pad, relu_in, B, D, H, W);
+}
+
 int dlcs_conv3d_k3(int dtype, const void* in, int64_t cin, int64_t cin_ld, const void* wpacked,
                    int64_t cin_pad, const float* bias, void* out, int out_dtype, int64_t cout,
                    int64_t cout_pad, int64_t cout_ld, int64_t B, int64_t D, int64_t H, int64_t W,
                    int relu_in, const void* mask, int64_t mask_ld, const void* residual, int res_dtype,
-                   int64_t res_ld, float res_scale, int accumulate, int relu_out, dlcs_stream_t stream) {
+                   int64_t res_ld, float res_scale, int accumulate, int relu_out, void* workspace,
+                   size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(in && wpacked && out && B > 0);
     if (D % 4 || H % 4 || W % 4 || cin_pad % CK || cout_pad % 32 || cin_ld % 8 || cin > cin_pad || cout > cout_pad)
         return DLCS_ERR_UNSUPPORTED_SIZE;
+    if (!ws_ok(workspace, workspace_bytes, conv_k3_ws_bytes(dtype, cin, cin_pad, cout, cout_pad, relu_in, B, D, H, W)))
+        return DLCS_ERR_WORKSPACE;
     ConvArgs a{};
     a.in = in; a.w = wpacked; a.bias = bias; a.out = out; a.mask = mask; a.res = residual;
     a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)cin; a.cin_ld = (int)cin_ld;
@@ -1961,16 +1948,26 @@ int dlcs_conv3d_k3(int dtype, const void* in, int64_t cin, int64_t cin_ld, const
     a.res_f32 = (res_dtype == DLCS_F32); a.accumulate = accumulate; a.res_scale = res_scale;
     a.relu_out = relu_out;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == DLCS_F32 ? conv_launch<float>(a, st) : conv_launch<bf16>(a, st);
+    float* ws = static_cast<float*>(workspace);
+    return dtype == DLCS_F32 ? conv_launch<float>(a, ws, st) : conv_launch<bf16>(a, ws, st);
+}
+
+size_t dlcs_conv3d_k3_wgrad_workspace_bytes(int dtype, int64_t cin, int64_t cin_pad, int64_t cout, int64_t cout_pad,
+                                            int relu_in, int has_dbias, int64_t B, int64_t D, int64_t H, int64_t W) {
+    return wgrad_k3_ws_bytes(dtype, cin, cin_pad, cout, cout_pad, relu_in, has_dbias != 0,
+                             B * (D / 4) * (H / 4) * (W / 4));
 }
 
 int dlcs_conv3d_k3_wgrad(int dtype, const void* in, int64_t cin, int64_t cin_ld, int64_t cin_pad, int relu_in,
                          const void* gout, int64_t cout, int64_t g_ld, int64_t cout_pad, float* dw_packed,
                          float* dbias, int64_t B, int64_t D, int64_t H, int64_t W, int64_t vox_per_block,
-                         dlcs_stream_t stream) {
+                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(in && gout && dw_packed && B > 0);
     if (D % 4 || H % 4 || W % 4 || cin_pad % 32 || cout_pad % 32 || cout_pad > 160 || cin_ld % 8 || g_ld % 8)
         return DLCS_ERR_UNSUPPORTED_SIZE;
+    if (!ws_ok(workspace, workspace_bytes, wgrad_k3_ws_bytes(dtype, cin, cin_pad, cout, cout_pad, relu_in, dbias != nullptr,
+                                                             B * (D / 4) * (H / 4) * (W / 4))))
+        return DLCS_ERR_WORKSPACE;
     WgradArgs a{};
     a.in = in; a.g = gout; a.dw = dw_packed;
     a.B = (int)B; a.D = (int)D; a.H = (int)H; a.W = (int)W; a.Cin = (int)cin; a.cin_ld = (int)cin_ld;
@@ -1979,7 +1976,8 @@ int dlcs_conv3d_k3_wgrad(int dtype, const void* in, int64_t cin, int64_t cin_ld,
     hipStream_t st = (hipStream_t)stream;
     a.dbias = dbias;
     bool done = false;                            // the 160-channel bf16 kernel sums the columns itself
-    const int rc = dtype == DLCS_F32 ? wgrad_launch<float>(a, st, &done) : wgrad_launch<bf16>(a, st, &done);
+    float* ws = static_cast<float*>(workspace);
+    const int rc = dtype == DLCS_F32 ? wgrad_launch<float>(a, ws, st, &done) : wgrad_launch<bf16>(a, ws, st, &done);
     if (rc || !dbias || done) return rc;
     const long rows = B * D * H * W;
     return dlcs_colsum(dtype, gout, rows, cout, g_ld, dbias, stream);
@@ -2054,10 +2052,16 @@ int dlcs_conv3d_k3_wgrad_x6(const void* xa, const void* xb, const void* ga, cons
 // 640-B zero row (the weight gradient's source for halo voxels off the grid)
 size_t dlcs_split2_f16_bytes(int64_t rows) { return (size_t)rows * 640 + 256 + 640; }
 
+size_t dlcs_split2_f16_workspace_bytes(int64_t rows, int has_colsum) {
+    return has_colsum ? (size_t)split2_blocks(rows) * 160 * sizeof(float) : 0;
+}
+
 int dlcs_split2_f16(const float* x, int64_t rows, int64_t ld, void* planes, int have_max, float* colsum,
-                    dlcs_stream_t stream) {
+                    void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(x && planes && rows > 0 && ld >= 160);
     if (ld % 4 || ((uintptr_t)x & 15) || ((uintptr_t)planes & 15)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    if (!ws_ok(workspace, workspace_bytes, dlcs_split2_f16_workspace_bytes(rows, colsum != nullptr)))
+        return DLCS_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     unsigned* mx = (unsigned*)((char*)planes + (size_t)rows * 640);
     if (!have_max) {
@@ -2065,11 +2069,9 @@ int dlcs_split2_f16(const float* x, int64_t rows, int64_t ld, void* planes, int 
         hipLaunchKernelGGL(absmax_kernel, dim3(std::min(h3_grid(rows * 10), 2048u)), dim3(256), 0, st, x, (long)rows,
                            (int)ld, mx);
     }
-    // grid stride a multiple of 20 (each thread keeps one 8-channel group)
-    const unsigned g = (unsigned)std::min<long>(kSplit2Blocks, std::max<long>(5, (rows * 20 + 255) / 256 / 5 * 5));
+    const unsigned g = split2_blocks(rows);
     if (colsum) {
-        float* cpart = split2_colsum_workspace(st);
-        if (!cpart) return (int)hipErrorOutOfMemory;
+        float* cpart = static_cast<float*>(workspace);          // one row of 160 per block
         hipLaunchKernelGGL(split2_f16_kernel<true>, dim3(g), dim3(256), 0, st, x, (long)rows, (int)ld,
                            (const unsigned*)mx, (f16*)planes, cpart);
         hipLaunchKernelGGL(colsum_parts_kernel, dim3(160), dim3(256), 0, st, (const float*)cpart, (int)g, colsum);
@@ -2095,16 +2097,21 @@ int dlcs_conv3d_pack_weights_f16x3(const float* w, int mode, void* packed, dlcs_
 }
 
 // column-sum partials of the producers that also sum their output's columns (the
-// f16x3 conv: one row of 160 per tile; the K = 160 GEMM: per 64 x 160 tile)
-static float* colsum_part_workspace(hipStream_t st, long nwg) {
-    return static_cast<float*>(scratch(kScrColsum, st, (size_t)nwg * 160 * sizeof(float)));
+// f16x3 convs: one row of 160 per tile; the K = 160 GEMM: per 64 x 160 tile)
+static size_t colsum_part_bytes(long nwg, bool colsum) { return colsum ? (size_t)nwg * 160 * sizeof(float) : 0; }
+static long gemm_k160_tiles(long M, long N) { return (long)cdiv(M, 64) * (N / 160); }
+
+// the column-sum partials, then (at a 256-B offset) the tail split's partial tiles
+size_t dlcs_conv3d_k3_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int has_colsum) {
+    const long ntile = conv_tiles(B, D, H, W);
+    return ws_align(colsum_part_bytes(ntile, has_colsum != 0)) + conv_tail_bytes(ntile);
 }
 
 int dlcs_conv3d_k3_f16x3(const void* xplanes, const void* wpacked, const float* bias, float* out, int64_t cout_ld,
                          int64_t B, int64_t D, int64_t H, int64_t W, const float* mask, int64_t mask_ld,
                          const float* residual, int64_t res_ld, float res_scale, int accumulate, int relu_out,
                          unsigned* out_max, void* out_planes, float* colsum, const void* mask_planes,
-                         dlcs_stream_t stream) {
+                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(xplanes && wpacked && B > 0 && (out || (out_planes && !accumulate)) && !(mask && mask_planes));
     if (!out) cout_ld = 160;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
@@ -2134,19 +2141,25 @@ int dlcs_conv3d_k3_f16x3(const void* xplanes, const void* wpacked, const float* 
     v.exp = h3_exp;
 #endif
     hipStream_t st = (hipStream_t)stream;
-    const long ntile = (long)B * (D / 4) * ((H / 4 + 1) / 2) * ((W / 4 + 1) / 2);
-    if (colsum) {
-        v.cpart = colsum_part_workspace(st, ntile);           // one row of 160 per tile
-        if (!v.cpart) return (int)hipErrorOutOfMemory;
-    }
-    const int rc = conv_f16x3_launch(v, st);
+    const long ntile = conv_tiles(B, D, H, W);
+    if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_k3_f16x3_workspace_bytes(B, D, H, W, colsum != nullptr)))
+        return DLCS_ERR_WORKSPACE;
+    if (colsum) v.cpart = static_cast<float*>(workspace);     // one row of 160 per tile
+    float* tail_ws = reinterpret_cast<float*>(static_cast<char*>(workspace) +
+                                              ws_align(colsum_part_bytes(ntile, colsum != nullptr)));
+    const int rc = conv_f16x3_launch(v, tail_ws, st);
     if (rc || !colsum) return rc;
     hipLaunchKernelGGL(colsum_parts_kernel, dim3(160), dim3(256), 0, st, (const float*)v.cpart, (int)ntile, colsum);
     return dlcs_launch_status();
 }
 
+size_t dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W) {
+    return (size_t)wgh3_ranges(B * (D / 4) * (H / 4) * (W / 4), true).nr * kWgSlabBytes;
+}
+
 int dlcs_conv3d_k3_wgrad_f16x3(const void* xplanes, const void* gplanes, float* dw_packed, int64_t B, int64_t D,
-                               int64_t H, int64_t W, dlcs_stream_t stream) {
+                               int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
+                               dlcs_stream_t stream) {
     DLCS_CHECK_ARG(xplanes && gplanes && dw_packed && B > 0);
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     const long rows = (long)B * D * H * W;
@@ -2157,14 +2170,21 @@ int dlcs_conv3d_k3_wgrad_f16x3(const void* xplanes, const void* gplanes, float* 
     v.xmax = (const unsigned*)((const char*)xplanes + rows * 640);
     v.gmax = (const unsigned*)((const char*)gplanes + rows * 640);
     v.dw = dw_packed; v.B = (int)B; v.D = (int)D; v.H = (int)H; v.W = (int)W;
+    if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(B, D, H, W)))
+        return DLCS_ERR_WORKSPACE;
+    v.part = static_cast<float*>(workspace);
     return wgrad_f16x3_launch(v, (hipStream_t)stream);
+}
+
+size_t dlcs_gemm_k160_f16x3_workspace_bytes(int64_t M, int64_t N, int has_colsum) {
+    return colsum_part_bytes(gemm_k160_tiles(M, N), has_colsum != 0);
 }
 
 int dlcs_gemm_k160_f16x3(const void* aplanes, int64_t M, const void* bplanes, int64_t N, float* C, int64_t ldc,
                          const float* bias, int act, float alpha, const float* residual, int64_t ldr, float res_scale,
                          const float* residual2, int64_t ldr2, float res2_scale, int accumulate, unsigned* out_max,
                          void* out_planes, float* colsum, const void* res_planes, const void* res2_planes,
-                         dlcs_stream_t stream) {
+                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(aplanes && bplanes && M > 0 && N > 0 && (act == 0 || act == 3) &&
                    (C || (out_planes && !accumulate)) && !(residual && res_planes) && !(residual2 && res2_planes));
     if (!C) ldc = N;
@@ -2198,11 +2218,11 @@ int dlcs_gemm_k160_f16x3(const void* aplanes, int64_t M, const void* bplanes, in
         g.opmax = (const unsigned*)((const char*)out_planes + M * (N / 160) * 640);
     }
     hipStream_t st = (hipStream_t)stream;
-    const long nwg = cdiv(M, 64) * (N / 160);
+    const long nwg = gemm_k160_tiles(M, N);
     if (colsum) {
         if (g.row_map || nwg > (1L << 24)) return DLCS_ERR_UNSUPPORTED_SIZE;
-        g.cpart = colsum_part_workspace(st, nwg);
-        if (!g.cpart) return (int)hipErrorOutOfMemory;
+        if (!ws_ok(workspace, workspace_bytes, colsum_part_bytes(nwg, true))) return DLCS_ERR_WORKSPACE;
+        g.cpart = static_cast<float*>(workspace);
     }
     const int rc = gemm_k160_launch(g, st);
     if (rc || !colsum) return rc;
@@ -2267,14 +2287,19 @@ int dlcs_h3r_pack_multi(int n, const float* const* src, const int64_t* ld, const
     return 0;
 }
 
-// partial-tile buffer of the split-K h3r
-static float* h3r_ksplit_workspace(hipStream_t st, size_t floats) {
-    return static_cast<float*>(scratch(kScrH3r, st, floats * sizeof(float)));
+// deep K with a plain epilogue runs split over K: at most 8 raw partial tiles [M][N]
+static bool h3r_deep_k(long K, long N, int act, bool row_map, bool aux_out) {
+    return N % 160 == 0 && K % 160 == 0 && K / 160 >= 16 && act == 0 && !row_map && !aux_out;
+}
+
+size_t dlcs_gemm_h3r_workspace_bytes(int64_t M, int64_t K, int64_t N, int act, int has_row_map, int has_aux_out) {
+    return h3r_deep_k(K, N, act, has_row_map != 0, has_aux_out != 0) ? (size_t)8 * M * N * sizeof(float) : 0;
 }
 
 int dlcs_gemm_h3r(const float* A, int64_t M, int64_t K, int64_t lda, const void* bpacked, int64_t N, float* C,
                   int64_t ldc, const float* bias, int act, const float* aux, float* aux_out, int64_t ldaux, float alpha,
-                  const float* residual, int64_t ldr, const int32_t* row_map, int accumulate, dlcs_stream_t stream) {
+                  const float* residual, int64_t ldr, const int32_t* row_map, int accumulate, void* workspace,
+                  size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(A && bpacked && C && M > 0 && N > 0 && K > 0 && act >= 0 && act <= 7 &&
                    ((act != 2 && act != 5 && act != 6) || aux) && lda >= K);
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
@@ -2287,6 +2312,9 @@ int dlcs_gemm_h3r(const float* A, int64_t M, int64_t K, int64_t lda, const void*
         (residual && (ldr % 4 || !al16(residual))) || ((aux || aux_out) && ldaux % 4) || (aux && !al16(aux)) ||
         (aux_out && !al16(aux_out)) || M >= (1L << 31) || K > 16384 || N * K * 4 >= (1L << 31))
         return DLCS_ERR_UNSUPPORTED_SIZE;
+    if (!ws_ok(workspace, workspace_bytes,
+               dlcs_gemm_h3r_workspace_bytes(M, K, N, act, row_map != nullptr, aux_out != nullptr)))
+        return DLCS_ERR_WORKSPACE;
     GemmH3rArgs g{};
     g.a = A; g.lda = lda; g.M = (int)M;
     g.bp = (const f16*)bpacked; g.binv = (const float*)((const char*)bpacked + N * K * 4); g.N = (int)N;
@@ -2303,12 +2331,11 @@ int dlcs_gemm_h3r(const float* A, int64_t M, int64_t K, int64_t lda, const void*
     // tiles summed in a fixed order by h3r_ksplit_reduce_kernel.  tools/embed_bench.py:
     // 272 us unsplit, 238 / 250 / 235 us at 2 / 4 / 8 ranges (x6 NT GEMM: 290 us)
     g.ksplit = 1;
-    if (nj == 5 && K / 160 >= 16 && act == 0 && !row_map && !aux_out) {
+    if (h3r_deep_k(K, N, act, row_map != nullptr, aux_out != nullptr)) {
         static const int ks_env = [] { const char* e = dlcs_knob("DLCS_H3R_KSPLIT"); return e ? atoi(e) : 0; }();
         const int ks = ks_env == 1 || ks_env == 2 || ks_env == 4 || ks_env == 8 ? ks_env : 8;
         if (ks > 1) {
-            g.part = h3r_ksplit_workspace(st, (size_t)ks * M * N);
-            if (!g.part) return (int)hipErrorOutOfMemory;
+            g.part = static_cast<float*>(workspace);    // ks <= 8 partial tiles
             g.ksplit = ks;
         }
     }
@@ -2417,11 +2444,16 @@ int dlcs_absmax_f32(const float* x, int64_t n, unsigned* out, dlcs_stream_t stre
     return dlcs_launch_status();
 }
 
+size_t dlcs_conv3d_thin_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int has_colsum) {
+    return colsum_part_bytes(conv_tiles(B, D, H, W), has_colsum != 0);
+}
+
 int dlcs_conv3d_thin_f16x3(const float* in, int64_t cin, int64_t cin_ld, const unsigned* in_max, const void* wthin,
                            const float* bias, float* out, int64_t cout, int64_t cout_ld, int64_t B, int64_t D,
                            int64_t H, int64_t W, const float* mask, int64_t mask_ld, const float* residual,
                            int64_t res_ld, float res_scale, int accumulate, int relu_out, unsigned* out_max,
-                           void* out_planes, float* colsum, const void* mask_planes, dlcs_stream_t stream) {
+                           void* out_planes, float* colsum, const void* mask_planes, void* workspace,
+                           size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(in && in_max && wthin && B > 0 && (out || out_planes) && !(mask && mask_planes));
     if (!out) cout_ld = 160;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
@@ -2446,12 +2478,9 @@ int dlcs_conv3d_thin_f16x3(const float* in, int64_t cin, int64_t cin_ld, const u
     if (mask_planes && !al16(mask_planes)) return DLCS_ERR_UNSUPPORTED_SIZE;
     if (out_planes && (!al16(out_planes) || cout_ld != 160)) return DLCS_ERR_UNSUPPORTED_SIZE;
     const unsigned* opmax = out_planes ? (const unsigned*)((const char*)out_planes + rows * 640) : nullptr;
-    const long ntile = (long)B * (D / 4) * ((H / 4 + 1) / 2) * ((W / 4 + 1) / 2);
-    float* cpart = nullptr;
-    if (colsum) {
-        cpart = colsum_part_workspace(st, ntile);
-        if (!cpart) return (int)hipErrorOutOfMemory;
-    }
+    const long ntile = conv_tiles(B, D, H, W);
+    if (!ws_ok(workspace, workspace_bytes, colsum_part_bytes(ntile, colsum != nullptr))) return DLCS_ERR_WORKSPACE;
+    float* cpart = colsum ? static_cast<float*>(workspace) : nullptr;
     const int rc = conv_thin_f16x3_launch(v, (const f16*)wthin, in_max, (int)cin, thin_in, st, (f16*)out_planes, opmax,
                                           cpart);
     if (rc || !colsum) return rc;
@@ -2502,10 +2531,12 @@ int dlcs_conv3d_thin_out_planes_f16x3(const void* xplanes, const void* wthin, co
     return conv_thin_out_p_launch(v, (const f16*)xplanes, (const f16*)wthin, (hipStream_t)stream);
 }
 
+size_t dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes(void) { return (size_t)kTwpWG * 160 * 128 * sizeof(float); }
+
 int dlcs_conv3d_thin_wgrad_planes_f16x3(const void* bigplanes, const float* thin, int64_t thin_ch, int64_t thin_ld,
                                         const unsigned* thin_max, int big_is_co, float* dw_packed, int64_t cout_pad,
-                                        int64_t cin_pad, int64_t B, int64_t D, int64_t H, int64_t W,
-                                        dlcs_stream_t stream) {
+                                        int64_t cin_pad, int64_t B, int64_t D, int64_t H, int64_t W, void* workspace,
+                                        size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(bigplanes && thin && thin_max && dw_packed && B > 0 && thin_ch >= 1 && thin_ch <= 4 &&
                    thin_ld >= 4);
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
@@ -2518,6 +2549,9 @@ int dlcs_conv3d_thin_wgrad_planes_f16x3(const void* bigplanes, const float* thin
     t.thin_ld = (int)thin_ld; t.sgn = big_is_co ? 1 : -1; t.big_is_co = big_is_co ? 1 : 0; t.thin_ch = (int)thin_ch;
     t.cout_pad = (int)cout_pad; t.cin_pad = (int)cin_pad;
     t.B = (int)B; t.D = (int)D; t.H = (int)H; t.W = (int)W;
+    if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes()))
+        return DLCS_ERR_WORKSPACE;
+    t.part = static_cast<float*>(workspace);                 // one [160][128] slab per workgroup
     return wgrad_thin_p_launch(t, (hipStream_t)stream);
 }
 

@@ -305,9 +305,10 @@ __global__ void __launch_bounds__(256) colsum_parts_kernel(const float* cpart, i
     if (threadIdx.x == 0) colsum[c] += red[0];
 }
 
-// per-block column-sum partials of the split (kSplit2Blocks x 160)
-static float* split2_colsum_workspace(hipStream_t st) {
-    return static_cast<float*>(scratch(kScrSplit2, st, (size_t)kSplit2Blocks * 160 * sizeof(float)));
+// workgroups of the split (one row of 160 column-sum partials each): the grid stride
+// is a multiple of 20 (each thread keeps one 8-channel group)
+static unsigned split2_blocks(long rows) {
+    return (unsigned)std::min<long>(kSplit2Blocks, std::max<long>(5, (rows * 20 + 255) / 256 / 5 * 5));
 }
 
 // weights [160][160][27] fp32 -> WP [5][27][160][64]; mode 0 (forward): rows co,
@@ -951,12 +952,8 @@ __global__ void __launch_bounds__(160) tail_colsum_kernel(ConvH3Args a, int npar
     a.cpart[(long)(a.tail_base + t) * 160 + c] = cs;
 }
 
-// workspace of the tail split (<= 51 tiles x 5 x 160 KB), per (device, stream)
-static float* h3_tail_workspace(hipStream_t st) {
-    return static_cast<float*>(scratch(kScrH3Tail, st, (size_t)51 * 5 * 256 * 160 * sizeof(float)));
-}
-
-static int conv_f16x3_launch(const ConvH3Args& v0, hipStream_t st) {
+// tail_ws: conv_tail_bytes(tiles) bytes for the tail split's partial tiles
+static int conv_f16x3_launch(const ConvH3Args& v0, float* tail_ws, hipStream_t st) {
     ConvH3Args v = v0;
     const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
     unsigned nblk = (unsigned)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
@@ -965,14 +962,9 @@ static int conv_f16x3_launch(const ConvH3Args& v0, hipStream_t st) {
     // workgroups plus a fixed-order reduce
     const char* te = dlcs_test_hook("DLCS_H3_TAIL");                 // read per launch (tests toggle it)
     const bool tail_split = !(te && te[0] == '0');
-    const unsigned ntail = nblk % 256, nmain = nblk - ntail;
-    const bool split = tail_split && nmain > 0 && ntail > 0 && ntail * 5 <= 256;
-    float* ws = nullptr;
-    if (split) {
-        ws = h3_tail_workspace(st);
-        if (!ws) return (int)hipErrorOutOfMemory;
-        nblk = nmain;
-    }
+    const unsigned ntail = tail_split ? conv_tail_tiles(nblk) : 0u, nmain = nblk - ntail;
+    const bool split = ntail > 0;
+    if (split) nblk = nmain;
     int epi;
     if (!v.res && !v.mask && !v.mplanes && !v.accumulate) epi = 0;
     else if (v.res && !v.mask && !v.mplanes && !v.accumulate) epi = kEpiRes;
@@ -1010,7 +1002,7 @@ static int conv_f16x3_launch(const ConvH3Args& v0, hipStream_t st) {
     else launch(std::integral_constant<int, 0>{});
     if (split) {
         ConvH3Args t = v;
-        t.part = ws;
+        t.part = tail_ws;
         t.tail_base = (int)nmain;
 #ifdef DLCS_DIAG_BUILD
         if (pf == 1) hipLaunchKernelGGL((conv3d_k3_f16x3_kernel<0, 1, true>), dim3(ntail * 5), dim3(512), 0, st, t);
@@ -1298,15 +1290,17 @@ __global__ void __launch_bounds__(256) wgrad_f16x3_reduce_kernel(WgradH3Args a, 
     *d = *d + s * inv;
 }
 
-// partial slabs of the weight gradient (<= 32 ranges x 2.76 MB), per (device, stream)
+// voxel ranges of the weight gradient, one partial slab (2.76 MB) each: 28, or
+// DLCS_WGH3_RANGES (DIAG build) up to 32; bound = the most any setting gives
 constexpr int kWgH3MaxRanges = 32;
 
-static float* wgh3_workspace(hipStream_t st) {
-    return static_cast<float*>(scratch(kScrWgH3, st, (size_t)kWgH3MaxRanges * 27 * 160 * 160 * sizeof(float)));
+static PatchRanges wgh3_ranges(long npatch, bool bound) {
+    static const int env_nr = [] { const char* e = dlcs_knob("DLCS_WGH3_RANGES"); return e ? atoi(e) : 0; }();
+    return patch_ranges(npatch, bound ? kWgH3MaxRanges : env_nr > 0 ? std::min(env_nr, kWgH3MaxRanges) : 28);
 }
 
-static int wgrad_f16x3_launch(const WgradH3Args& a0, hipStream_t st) {
-    WgradH3Args a = a0;
+// a.part: wgh3_ranges(npatch, true).nr slabs
+static int wgrad_f16x3_launch(const WgradH3Args& a, hipStream_t st) {
     const long npatch = (long)a.B * (a.D / 4) * (a.H / 4) * (a.W / 4);
     // 32-bit lane offsets (16-B units << 7 in the kernel, relative to a base bias_rows below
     // the patch): 2 bias_rows + 2 patches within 2^25 x 16 B; the zero row's byte offset
@@ -1314,13 +1308,9 @@ static int wgrad_f16x3_launch(const WgradH3Args& a0, hipStream_t st) {
     const long bias_rows = ((long)(a.H / 4) * (a.W / 4) + a.W / 4 + 1) * 64;
     if ((2 * bias_rows + 128) * 40 >= (1L << 25) || (npatch * 64 + bias_rows) * 640 + 1024 >= (1L << 32))
         return DLCS_ERR_UNSUPPORTED_SIZE;
-    static const int env_nr = [] { const char* e = dlcs_knob("DLCS_WGH3_RANGES"); return e ? atoi(e) : 0; }();
-    int nr = env_nr > 0 ? std::min(env_nr, kWgH3MaxRanges) : 28;
-    nr = (int)std::min<long>(nr, npatch);
-    const long pp = (npatch + nr - 1) / nr;
-    nr = (int)((npatch + pp - 1) / pp);
-    a.part = wgh3_workspace(st);
-    if (!a.part) return (int)hipErrorOutOfMemory;
+    const PatchRanges r = wgh3_ranges(npatch, false);
+    const int nr = r.nr;
+    const long pp = r.pp;
     hipLaunchKernelGGL(conv3d_wgrad_f16x3_kernel, dim3((unsigned)(9 * nr)), dim3(768), 0, st, a, nr, (int)pp);
     hipLaunchKernelGGL(wgrad_f16x3_reduce_kernel, dim3((unsigned)cdiv(27L * 160 * 40, 256)), dim3(256), 0, st, a, nr);
     return dlcs_launch_status();

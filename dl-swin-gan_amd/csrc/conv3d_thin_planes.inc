@@ -579,14 +579,12 @@ __global__ void __launch_bounds__(256) wgrad_thin_p_reduce_kernel(ThinWgPArgs a,
     *d += v * inv;
 }
 
-// partial slabs (256 workgroups x [160][128]), per (device, stream)
+// a.part: partial slabs (256 workgroups x [160][128])
 constexpr int kTwpWG = 256;
 
-static int wgrad_thin_p_launch(ThinWgPArgs a, hipStream_t st) {
+static int wgrad_thin_p_launch(const ThinWgPArgs& a, hipStream_t st) {
     const long npatch = (long)a.B * (a.D / 4) * (a.H / 4) * (a.W / 4);
     if (npatch * 64 * 640 >= (1L << 32)) return DLCS_ERR_UNSUPPORTED_SIZE;       // 32-bit DMA offsets
-    a.part = static_cast<float*>(scratch(kScrTwp, st, (size_t)kTwpWG * 160 * 128 * sizeof(float)));
-    if (!a.part) return (int)hipErrorOutOfMemory;
     const int ppr = (int)((npatch + kTwpWG - 1) / kTwpWG);
     hipLaunchKernelGGL(conv3d_wgrad_thin_p_kernel, dim3(kTwpWG), dim3(512), 0, st, a, ppr);
     hipLaunchKernelGGL(wgrad_thin_p_reduce_kernel, dim3(160 * 128 / 64), dim3(256), 0, st, a, kTwpWG);

@@ -298,19 +298,15 @@ __global__ void __launch_bounds__(256) conv_v6_tail_reduce_kernel(ConvV6Args g, 
     }
 }
 
-// the tail split's partial tiles (<= 51 tiles x 5 x 160 KB), per (device, stream)
-static float* v6_tail_workspace(hipStream_t st) {
-    return static_cast<float*>(scratch(kScrV6Tail, st, (size_t)51 * 5 * 256 * 160 * sizeof(float)));
-}
-
-static int conv_v6_launch(const ConvV2Args& v, hipStream_t st) {
+// tail_ws: conv_tail_bytes(tiles) bytes for the tail split's partial tiles
+static int conv_v6_launch(const ConvV2Args& v, float* tail_ws, hipStream_t st) {
     if ((long)v.B * v.D * v.H * v.W * v.cin_ld >= (1L << 31)) return DLCS_ERR_UNSUPPORTED_SIZE;   // 32-bit halo offsets
     const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
     const unsigned nblk = (unsigned)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
     const char* te = dlcs_test_hook("DLCS_V6_TAIL");                 // read per launch (tests toggle it)
     const bool tail_split = !(te && te[0] == '0');
-    const unsigned ntail = nblk % 256, nmain = nblk - ntail;
-    const bool split = tail_split && nmain > 0 && ntail > 0 && ntail * 5 <= 256;
+    const unsigned ntail = tail_split ? conv_tail_tiles(nblk) : 0u, nmain = nblk - ntail;
+    const bool split = ntail > 0;
     ConvV6Args g{};
     g.v = v;
 #ifdef DLCS_DIAG_BUILD
@@ -319,10 +315,7 @@ static int conv_v6_launch(const ConvV2Args& v, hipStream_t st) {
         g.exp = e ? atoi(e) : 0;
     }
 #endif
-    if (split) {
-        g.part = v6_tail_workspace(st);
-        if (!g.part) return (int)hipErrorOutOfMemory;
-    }
+    if (split) g.part = tail_ws;
     int epi;
     if (!v.res && !v.mask && !v.accumulate && !v.out_f32) epi = 0;
     else if (v.res && !v.res_f32 && !v.mask && !v.accumulate && !v.out_f32) epi = kEpiRes;

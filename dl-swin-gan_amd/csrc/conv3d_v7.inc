@@ -317,15 +317,16 @@ __global__ void __launch_bounds__(256) conv_v7_tail_reduce_kernel(ConvV6Args g, 
     }
 }
 
-static int conv_v7_launch(const ConvV2Args& v, hipStream_t st) {
+// tail_ws: conv_tail_bytes(tiles) bytes, as v6 (twice the tail units of half the channels)
+static int conv_v7_launch(const ConvV2Args& v, float* tail_ws, hipStream_t st) {
     if ((long)v.B * v.D * v.H * v.W * v.cin_ld >= (1L << 31)) return DLCS_ERR_UNSUPPORTED_SIZE;   // 32-bit halo offsets
     const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
     const unsigned nunit = 2u * (unsigned)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
     const char* te = dlcs_test_hook("DLCS_V7_TAIL");                 // read per launch (tests toggle it)
     const bool tail_split = !(te && te[0] == '0');
-    // one round = 512 workgroups (two per CU)
-    const unsigned ntail = nunit % 512, nmain = nunit - ntail;
-    const bool split = tail_split && nmain > 0 && ntail > 0 && ntail * 5 <= 512;
+    // one round = 512 workgroups (two per CU): the units of v6's tail tiles
+    const unsigned ntail = tail_split ? 2u * conv_tail_tiles(nunit / 2) : 0u, nmain = nunit - ntail;
+    const bool split = ntail > 0;
     ConvV6Args g{};
     g.v = v;
 #ifdef DLCS_DIAG_BUILD
@@ -334,10 +335,7 @@ static int conv_v7_launch(const ConvV2Args& v, hipStream_t st) {
         g.exp = e ? atoi(e) : 0;
     }
 #endif
-    if (split) {
-        g.part = v6_tail_workspace(st);                 // <= 102 units x 5 x 256 x 80 floats: the v6 workspace's size
-        if (!g.part) return (int)hipErrorOutOfMemory;
-    }
+    if (split) g.part = tail_ws;                        // ntail units x 5 x 256 x 80 floats
     int epi;
     if (!v.res && !v.mask && !v.accumulate && !v.out_f32) epi = 0;
     else if (v.res && !v.res_f32 && !v.mask && !v.accumulate && !v.out_f32) epi = kEpiRes;

@@ -25,8 +25,6 @@ _SZ = ctypes.c_size_t
 SIGNATURES = {
     "dlcs_version": [],
     "dlcs_status_string": [_INT],
-    "dlcs_scratch_bytes": [],
-    "dlcs_release_scratch": [],
     "dlcs_sense_workspace_bytes": [_I64, _I64, _I64, _I64, _I64],
     "dlcs_sense_fwd": [_P, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P],
     "dlcs_sense_adj": [_P, _P, _P, _I64, _P, _P, _P, _F, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P],
@@ -58,39 +56,49 @@ SIGNATURES = {
                              _I64, _I64, _I64, _F, _P],
     "dlcs_window_attn_bwd": [_INT, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64,
                              _I64, _I64, _I64, _F, _P],
+    "dlcs_conv3d_k3_workspace_bytes": [_INT, _I64, _I64, _I64, _I64, _INT, _I64, _I64, _I64, _I64],
     "dlcs_conv3d_k3": [_INT, _P, _I64, _I64, _P, _I64, _P, _P, _INT, _I64, _I64, _I64, _I64, _I64, _I64,
-                       _I64, _INT, _P, _I64, _P, _INT, _I64, _F, _INT, _INT, _P],
+                       _I64, _INT, _P, _I64, _P, _INT, _I64, _F, _INT, _INT, _P, _SZ, _P],
+    "dlcs_conv3d_k3_wgrad_workspace_bytes": [_INT, _I64, _I64, _I64, _I64, _INT, _INT, _I64, _I64, _I64, _I64],
     "dlcs_conv3d_k3_wgrad": [_INT, _P, _I64, _I64, _I64, _INT, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64,
-                             _I64, _I64, _P],
+                             _I64, _I64, _P, _SZ, _P],
     "dlcs_conv3d_pack_weights": [_INT, _P, _P, _I64, _I64, _I64, _I64, _INT, _P],
     "dlcs_conv3d_unpack_wgrad": [_P, _P, _I64, _I64, _I64, _I64, _INT, _P],
     "dlcs_split2_f16_bytes": [_I64],
-    "dlcs_split2_f16": [_P, _I64, _I64, _P, _INT, _P, _P],
+    "dlcs_split2_f16_workspace_bytes": [_I64, _INT],
+    "dlcs_split2_f16": [_P, _I64, _I64, _P, _INT, _P, _P, _SZ, _P],
     "dlcs_conv3d_pack_weights_f16x3_bytes": [],
     "dlcs_conv3d_pack_weights_f16x3": [_P, _INT, _P, _P],
+    "dlcs_gemm_k160_f16x3_workspace_bytes": [_I64, _I64, _INT],
     "dlcs_gemm_k160_f16x3": [_P, _I64, _P, _I64, _P, _I64, _P, _INT, _F, _P, _I64, _F, _P, _I64, _F, _INT, _P, _P, _P,
-                             _P, _P, _P],
+                             _P, _P, _P, _SZ, _P],
     "dlcs_planes_bound": [_P, _I64, _P, _P, _F, _P, _P, _F, _P, _I64, _F, _P],
     "dlcs_abs_row_sum_max": [_P, _I64, _I64, _I64, _I64, _I64, _P, _P],
     "dlcs_h3r_pack_bytes": [_I64, _I64],
     "dlcs_h3r_pack_multi": [_INT, _P, _P, _P, _P, _P, _P, _P],
-    "dlcs_gemm_h3r": [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _INT, _P, _P, _I64, _F, _P, _I64, _P, _INT, _P],
+    "dlcs_gemm_h3r_workspace_bytes": [_I64, _I64, _I64, _INT, _INT, _INT],
+    "dlcs_gemm_h3r": [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _INT, _P, _P, _I64, _F, _P, _I64, _P, _INT, _P, _SZ,
+                      _P],
     "dlcs_f8r_quant": [_P, _I64, _I64, _I64, _P, _P, _P],
     "dlcs_gemm_f8r": [_P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _INT, _P, _I64, _F, _P, _I64, _P, _P],
     "dlcs_linear_k160_f16x3": [_P, _I64, _P, _I64, _P, _I64, _P, _INT, _P, _P, _I64, _F, _P, _I64, _P, _INT, _P],
     "dlcs_gemm_f32_splitk_det": [_P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
     "dlcs_gemm_f32_splitk_det_workspace_bytes": [_I64, _I64],
-    "dlcs_conv3d_k3_wgrad_f16x3": [_P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes": [_I64] * 4,
+    "dlcs_conv3d_k3_wgrad_f16x3": [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _SZ, _P],
+    "dlcs_conv3d_k3_f16x3_workspace_bytes": [_I64, _I64, _I64, _I64, _INT],
     "dlcs_conv3d_k3_f16x3": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _F, _INT, _INT, _P, _P, _P,
-                             _P, _P],
+                             _P, _P, _SZ, _P],
     "dlcs_conv3d_thin_pack_f16x3_bytes": [_INT],
     "dlcs_conv3d_thin_pack_f16x3": [_P, _I64, _I64, _I64, _I64, _INT, _P, _P],
     "dlcs_absmax_f32": [_P, _I64, _P, _P],
+    "dlcs_conv3d_thin_f16x3_workspace_bytes": [_I64, _I64, _I64, _I64, _INT],
     "dlcs_conv3d_thin_f16x3": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P,
-                               _I64, _F, _INT, _INT, _P, _P, _P, _P, _P],
+                               _I64, _F, _INT, _INT, _P, _P, _P, _P, _P, _SZ, _P],
     "dlcs_conv3d_thin_out_planes_f16x3": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _INT, _P],
+    "dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes": [],
     "dlcs_conv3d_thin_wgrad_planes_f16x3": [_P, _P, _I64, _I64, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64,
-                                            _P],
+                                            _P, _SZ, _P],
     "dlcs_conv3d_thin_wgrad_f16x3": [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _I64, _I64,
                                      _I64, _P],
     "dlcs_swin_pre": [_INT, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
@@ -131,13 +139,9 @@ DIAG_SIGNATURES = {
     "dlcs_debug_conv_stamps": [_P, _I64],
     "dlcs_debug_h3_stamps": [_P, _I64],
 }
-_RESTYPE = {"dlcs_status_string": ctypes.c_char_p, "dlcs_scratch_bytes": _SZ, "dlcs_sense_workspace_bytes": _SZ,
-            "dlcs_sense_cg_workspace_bytes": _SZ, "dlcs_sense_rowtab_bytes": _SZ,
-            "dlcs_sense_rows_workspace_bytes": _SZ, "dlcs_split2_f16_bytes": _SZ,
-            "dlcs_conv3d_pack_weights_f16x3_bytes": _SZ, "dlcs_conv3d_thin_pack_f16x3_bytes": _SZ,
-            "dlcs_gemm_dw_workspace_bytes": _SZ, "dlcs_layernorm_bwd_workspace_bytes": _SZ,
-            "dlcs_gemm_f32_splitk_det_workspace_bytes": _SZ, "dlcs_gemm_nt_x6_workspace_bytes": _SZ,
-            "dlcs_h3r_pack_bytes": _SZ, "dlcs_mhsa_bwd_workspace_bytes": _SZ}
+# the size queries return size_t
+_RESTYPE = {name: _SZ for name in list(SIGNATURES) + list(DIAG_SIGNATURES) if name.endswith("_bytes")}
+_RESTYPE["dlcs_status_string"] = ctypes.c_char_p
 
 
 class DlcsError(RuntimeError):
@@ -167,16 +171,6 @@ def lib():
 def exported_symbols():
     """The product library's C-ABI (include/dlcs.h outside its DLCS_DIAG_BUILD blocks)."""
     return sorted(SIGNATURES.keys())
-
-
-def scratch_bytes():
-    """Bytes of the library's internal per-stream scratch buffers (dlcs.h)."""
-    return int(lib().dlcs_scratch_bytes())
-
-
-def release_scratch():
-    """Synchronise and free the library's internal scratch buffers (re-allocated on demand)."""
-    check(lib().dlcs_release_scratch(), "dlcs_release_scratch")
 
 
 def has_symbol(name):

@@ -34,6 +34,14 @@ def zeros(shape, dtype, device):
     return torch.zeros(shape, dtype=dtype, device=device)
 
 
+def _ws(name, device, *size_args):
+    """(buffer, bytes) for the workspace of entry point `name`: dlcs_<name>_workspace_bytes(*size_args)
+    bytes of uninitialised memory on `device`, or (None, 0) when the call needs none.  The caller
+    keeps the buffer until its launch has been issued and passes p(buffer), bytes."""
+    nb = int(getattr(_lib.lib(), name + "_workspace_bytes")(*size_args))
+    return (empty((nb,), torch.uint8, device), nb) if nb else (None, 0)
+
+
 # ---------------------------------------------------------------------------- GEMM
 GEMM_TRACE = None        # list -> per-call (shape key, start event, end event)
 
@@ -130,9 +138,10 @@ def linear_h3r(x, wpack, N, out=None, bias=None, act=0, aux=None, aux_out=None, 
     if out is None:
         out = empty((M if row_map is None else res.shape[0], N), torch.float32, x.device)
     ldaux = N if (aux is not None or aux_out is not None) else 0
+    ws, nb = _ws("dlcs_gemm_h3r", out.device, M, Kd, N, int(act), row_map is not None, aux_out is not None)
     call("dlcs_gemm_h3r", p(x), M, Kd, x.stride(0), p(wpack), N, p(out), out.stride(0), p(bias), int(act),
          p(aux), p(aux_out), ldaux, float(alpha), p(res), N if res is not None else 0, p(row_map),
-         int(accumulate), S())
+         int(accumulate), p(ws), nb, S())
     return out
 
 
@@ -352,11 +361,13 @@ def conv3d(x, cin, packed, cout, out_ld, grid, bias=None, out=None, out_dtype=No
     rows = B * D * H * W
     if out is None:
         out = empty((rows, out_ld), out_dtype or x.dtype, x.device)
+    ws, nb = _ws("dlcs_conv3d_k3", out.device, code(x), cin, packed.shape[2], cout, packed.shape[1], int(relu_in),
+             B, D, H, W)
     call("dlcs_conv3d_k3", code(x), p(x), cin, x.shape[-1], p(packed), packed.shape[2], p(bias),
          p(out), code(out), cout, packed.shape[1], out.shape[-1], B, D, H, W, int(relu_in),
          p(mask), mask.shape[-1] if mask is not None else 0, p(res),
          code(res) if res is not None else F32, res.shape[-1] if res is not None else 0,
-         float(res_scale), int(accumulate), int(relu_out), S())
+         float(res_scale), int(accumulate), int(relu_out), p(ws), nb, S())
     return out
 
 
@@ -404,7 +415,8 @@ def split2(x, out=None, have_max=False, colsum=None):
     rows = x.shape[0]
     if out is None:
         out = empty((int(_lib.lib().dlcs_split2_f16_bytes(rows)),), torch.uint8, x.device)
-    call("dlcs_split2_f16", p(x), rows, x.shape[-1], p(out), int(bool(have_max)), p(colsum), S())
+    ws, nb = _ws("dlcs_split2_f16", out.device, rows, colsum is not None)
+    call("dlcs_split2_f16", p(x), rows, x.shape[-1], p(out), int(bool(have_max)), p(colsum), p(ws), nb, S())
     return out
 
 
@@ -439,9 +451,10 @@ def conv3d_f16x3(planes, packed, grid, bias=None, out=None, mask=None, res=None,
     rows = B * D * H * W
     if out is None and not planes_only:
         out = empty((rows, 160), torch.float32, planes.device)
+    ws, nb = _ws("dlcs_conv3d_k3_f16x3", planes.device, B, D, H, W, colsum is not None)
     call("dlcs_conv3d_k3_f16x3", p(planes), p(packed), p(bias), p(out), out.shape[-1] if out is not None else 160,
          B, D, H, W, p(mask), mask.shape[-1] if mask is not None else 0, p(res), res.shape[-1] if res is not None else 0,
-         float(res_scale), int(accumulate), int(relu_out), out_max, p(out_planes), p(colsum), p(mask_planes), S())
+         float(res_scale), int(accumulate), int(relu_out), out_max, p(out_planes), p(colsum), p(mask_planes), p(ws), nb, S())
     return out
 
 
@@ -453,10 +466,11 @@ def gemm_k160_f16x3(a_planes, M, b_planes, N, C, bias=None, act=0, alpha=1.0, re
     [M N / 160][160], scale from the bound in their trailer (planes_bound); C None: planes only;
     colsum (fp32 [160]) += the column sums of that [M N / 160][160] view; res_planes / res2_planes:
     the residuals as split2 buffers of that view instead of fp32 res / res2."""
+    ws, nb = _ws("dlcs_gemm_k160_f16x3", a_planes.device, M, N, colsum is not None)
     call("dlcs_gemm_k160_f16x3", p(a_planes), M, p(b_planes), N, p(C), C.shape[-1] if C is not None else N,
          p(bias), int(act), float(alpha), p(res), res.shape[-1] if res is not None else 0, float(res_scale),
          p(res2), res2.shape[-1] if res2 is not None else 0, float(res2_scale), int(accumulate), out_max,
-         p(out_planes), p(colsum), p(res_planes), p(res2_planes), S())
+         p(out_planes), p(colsum), p(res_planes), p(res2_planes), p(ws), nb, S())
     return C
 
 
@@ -498,7 +512,8 @@ def linear_k160_f16x3(x_planes, M, w_planes, N, out, bias=None, act=0, aux=None,
 def conv3d_wgrad_f16x3(x_planes, g_planes, grid, dw_packed):
     """dw_packed [27, 160, 160] += fp32 conv weight gradient from f16 plane pairs (dlcs_conv3d_k3_wgrad_f16x3)."""
     B, D, H, W = grid
-    call("dlcs_conv3d_k3_wgrad_f16x3", p(x_planes), p(g_planes), p(dw_packed), B, D, H, W, S())
+    ws, nb = _ws("dlcs_conv3d_k3_wgrad_f16x3", dw_packed.device, B, D, H, W)
+    call("dlcs_conv3d_k3_wgrad_f16x3", p(x_planes), p(g_planes), p(dw_packed), B, D, H, W, p(ws), nb, S())
     return dw_packed
 
 
@@ -534,10 +549,11 @@ def conv3d_thin_f16x3(x, cin, x_max, wthin, cout, out_ld, grid, bias=None, out=N
     rows = B * D * H * W
     if out is None and not planes_only:
         out = empty((rows, out_ld), torch.float32, x.device)
+    ws, nb = _ws("dlcs_conv3d_thin_f16x3", x.device, B, D, H, W, colsum is not None)
     call("dlcs_conv3d_thin_f16x3", p(x), cin, x.shape[-1], _word(x_max), p(wthin), p(bias), p(out), cout,
          out.shape[-1] if out is not None else 160, B, D, H, W, p(mask), mask.shape[-1] if mask is not None else 0,
          p(res), res.shape[-1] if res is not None else 0, float(res_scale), int(accumulate), int(relu_out),
-         _word(out_max) if out_max is not None else None, p(out_planes), p(colsum), p(mask_planes), S())
+         _word(out_max) if out_max is not None else None, p(out_planes), p(colsum), p(mask_planes), p(ws), nb, S())
     return out
 
 
@@ -567,8 +583,9 @@ def conv3d_thin_wgrad_planes(big_planes, thin, thin_ch, thin_max, big_is_co, gri
     160-channel operand and the fp32 thin tensor (dlcs_conv3d_thin_wgrad_planes_f16x3); big_is_co:
     1 = SFE (planes = g), 0 = final conv (planes = its input)."""
     B, D, H, W = grid
+    ws, nb = _ws("dlcs_conv3d_thin_wgrad_planes_f16x3", dw_packed.device)
     call("dlcs_conv3d_thin_wgrad_planes_f16x3", p(big_planes), p(thin), thin_ch, thin.shape[-1], _word(thin_max),
-         int(big_is_co), p(dw_packed), dw_packed.shape[1], dw_packed.shape[2], B, D, H, W, S())
+         int(big_is_co), p(dw_packed), dw_packed.shape[1], dw_packed.shape[2], B, D, H, W, p(ws), nb, S())
     return dw_packed
 
 
@@ -576,8 +593,10 @@ def conv3d_wgrad(x, cin, relu_in, g, cout, grid, dw_packed, vox_per_block=16384,
     """dw_packed += the conv weight gradient; dbias (fp32 [cout], optional) += the bias
     gradient (column sums of g), fused into the 160-channel bf16 kernel."""
     B, D, H, W = grid
+    ws, nb = _ws("dlcs_conv3d_k3_wgrad", dw_packed.device, code(x), cin, dw_packed.shape[2], cout, dw_packed.shape[1],
+             int(relu_in), dbias is not None, B, D, H, W)
     call("dlcs_conv3d_k3_wgrad", code(x), p(x), cin, x.shape[-1], dw_packed.shape[2], int(relu_in),
-         p(g), cout, g.shape[-1], dw_packed.shape[1], p(dw_packed), p(dbias), B, D, H, W, vox_per_block, S())
+         p(g), cout, g.shape[-1], dw_packed.shape[1], p(dw_packed), p(dbias), B, D, H, W, vox_per_block, p(ws), nb, S())
     return dw_packed
 
 

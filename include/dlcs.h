@@ -41,14 +41,6 @@ typedef void* dlcs_stream_t; /* hipStream_t */
 
 int dlcs_version(void);
 const char* dlcs_status_string(int status);
-/* Library-internal scratch: a few per-(device, stream) partial buffers of the
- * fp32 split kernels (split-K / tail / slab partials, column sums; ~220 MB per
- * stream at the BASELINE slice), allocated with hipMalloc on first use and
- * kept for the process (outside torch's caching allocator).  bytes = their
- * total; release = synchronise the devices that own them and free them all
- * (they are re-allocated on the next launch that needs one).                */
-size_t dlcs_scratch_bytes(void);
-int dlcs_release_scratch(void);
 
 /* ---------------------------------------------------------------------------
  * SENSE operator -- tr:49-110 (SenseModel), tr:12-46 (FFT, ortho, uncentered).
@@ -261,20 +253,28 @@ int dlcs_window_attn_bwd(int dtype, const void* qkv, const void* out, const void
  *   epi: times (mask[row, co] > 0) if mask (ReLU backward); + res_scale * residual;
  *        then ReLU if relu_out (the consumer ConvBlock's pre-activation, s3d:256-259)
  * dgrad = the same call on weights packed with mode 1 (transposed, tap-flipped). */
+/* workspace: the partial tiles of the bf16 160 -> 160 kernel's tail split (0 for every other path). */
+size_t dlcs_conv3d_k3_workspace_bytes(int dtype, int64_t cin, int64_t cin_pad, int64_t cout, int64_t cout_pad,
+                                      int relu_in, int64_t B, int64_t D, int64_t H, int64_t W);
 int dlcs_conv3d_k3(int dtype, const void* in, int64_t cin, int64_t cin_ld, const void* wpacked,
                    int64_t cin_pad, const float* bias, void* out, int out_dtype, int64_t cout,
                    int64_t cout_pad, int64_t cout_ld, int64_t B, int64_t D, int64_t H, int64_t W,
                    int relu_in, const void* mask, int64_t mask_ld, const void* residual, int res_dtype,
-                   int64_t res_ld, float res_scale, int accumulate, int relu_out, dlcs_stream_t stream);
+                   int64_t res_ld, float res_scale, int accumulate, int relu_out, void* workspace,
+                   size_t workspace_bytes, dlcs_stream_t stream);
 /* dw_packed[tap][co][ci] += sum_v gout[v, co] * act(in)[v + off(tap), ci];
  * dbias (optional): dbias[co] += sum_v gout[v, co], the conv's bias gradient
  * (s3d:120-134) -- in the bf16 SFE weight gradient (thin input side) from the g
  * tiles it already holds (an all-ones MFMA operand, per-range partials summed in
  * a fixed order), otherwise by a column-sum launch after the weight gradient. */
+/* workspace: bf16 160 x 160: one dW partial slab per voxel range; bf16 thin input with dbias: one row of
+ * column sums per range; 0 for every other path (all of fp32). */
+size_t dlcs_conv3d_k3_wgrad_workspace_bytes(int dtype, int64_t cin, int64_t cin_pad, int64_t cout, int64_t cout_pad,
+                                            int relu_in, int has_dbias, int64_t B, int64_t D, int64_t H, int64_t W);
 int dlcs_conv3d_k3_wgrad(int dtype, const void* in, int64_t cin, int64_t cin_ld, int64_t cin_pad, int relu_in,
                          const void* gout, int64_t cout, int64_t g_ld, int64_t cout_pad, float* dw_packed,
                          float* dbias, int64_t B, int64_t D, int64_t H, int64_t W, int64_t vox_per_block,
-                         dlcs_stream_t stream);
+                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
 /* torch Conv3d weight w [cout][cin][3][3][3] fp32 -> packed (mode 0: [27][rows_pad=cout_pad][cols_pad=cin_pad];
  * mode 1 (dgrad): [27][rows_pad=cin_pad][cols_pad=cout_pad], taps flipped);
  * modes 2 / 3 (DIAG build; the product library returns DLCS_ERR_UNSUPPORTED_SIZE):
@@ -327,24 +327,30 @@ int dlcs_debug_h3_stamps(void* host, int64_t n);
  *   dlcs_conv3d_pack_weights_f16x3: w [160][160][3][3][3] fp32 -> packed
  *     (dlcs_conv3d_pack_weights_f16x3_bytes() bytes); mode 0 forward, 1 dgrad. */
 size_t dlcs_split2_f16_bytes(int64_t rows);
+/* workspace: per-workgroup column-sum partials (0 without colsum). */
+size_t dlcs_split2_f16_workspace_bytes(int64_t rows, int has_colsum);
 int dlcs_split2_f16(const float* x, int64_t rows, int64_t ld, void* planes, int have_max, float* colsum,
-                    dlcs_stream_t stream);
+                    void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
 size_t dlcs_conv3d_pack_weights_f16x3_bytes(void);
 int dlcs_conv3d_pack_weights_f16x3(const float* w, int mode, void* packed, dlcs_stream_t stream);
+/* workspace: per-tile column-sum partials (with colsum) and the partial tiles of the tail split. */
+size_t dlcs_conv3d_k3_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int has_colsum);
 int dlcs_conv3d_k3_f16x3(const void* xplanes, const void* wpacked, const float* bias, float* out, int64_t cout_ld,
                          int64_t B, int64_t D, int64_t H, int64_t W, const float* mask, int64_t mask_ld,
                          const float* residual, int64_t res_ld, float res_scale, int accumulate, int relu_out,
                          unsigned* out_max, void* out_planes, float* colsum, const void* mask_planes,
-                         dlcs_stream_t stream);
+                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
 /* C[m, n] (+)= alpha * act(sum_k A[m,k] B[n,k] + bias[n]) + res_scale res[m,n] + res2_scale res2[m,n]
  * for K = 160, A [M][160] and B [N][160] given as dlcs_split2_f16 plane pairs;
  * act 0 or 3 (ReLU); N a multiple of 160; C fp32 (the fp32 build's k4s4 patch
  * unembed forward and patch-embed input gradient, vst:455, :503). */
+/* workspace: per-tile column-sum partials (0 without colsum). */
+size_t dlcs_gemm_k160_f16x3_workspace_bytes(int64_t M, int64_t N, int has_colsum);
 int dlcs_gemm_k160_f16x3(const void* aplanes, int64_t M, const void* bplanes, int64_t N, float* C, int64_t ldc,
                          const float* bias, int act, float alpha, const float* residual, int64_t ldr, float res_scale,
                          const float* residual2, int64_t ldr2, float res2_scale, int accumulate, unsigned* out_max,
                          void* out_planes, float* colsum, const void* res_planes, const void* res2_planes,
-                         dlcs_stream_t stream);
+                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
 /* Producer-side split (no dlcs_split2_f16 pass over the fp32 output):
  *   out_planes (conv above, residual or mask form only, cout_ld = 160; the K = 160
  *     GEMM with ldc = N, viewed as [M N / 160][160]): the epilogue also writes the
@@ -393,7 +399,7 @@ int dlcs_linear_k160_f16x3(const void* xplanes, int64_t M, const void* wplanes, 
  * src[i][r * ld[i] + k] (r < rows[i], k < K[i], K % 32 == 0) into dst[i]
  * (dlcs_h3r_pack_bytes(rows, K) bytes, 16-B aligned): fp16 planes
  * [rows][K / 32][xh 32 | xl 32] with one power-of-two scale per row, then 1 / scale
- * per row (fp32), then the row-max partials (scratch).  dlcs_gemm_h3r:
+ * per row (fp32), then the row-max partials.  dlcs_gemm_h3r:
  *   C[row(m), n] (+)= alpha act(sum_k A[m, k] B[n, k] + bias[n]) + res[row(m), n]
  * with A fp32 [M, K] (row stride lda) split inside the kernel with one scale per
  * row (per row and 192-wide K segment when K is not one of the Swin sizes), B a
@@ -406,9 +412,13 @@ int dlcs_linear_k160_f16x3(const void* xplanes, int64_t M, const void* wplanes, 
 size_t dlcs_h3r_pack_bytes(int64_t rows, int64_t K);
 int dlcs_h3r_pack_multi(int n, const float* const* src, const int64_t* ld, const int* trans, const int64_t* rows,
                         const int64_t* K, void* const* dst, dlcs_stream_t stream);
+/* workspace: the split-K partial tiles of the deep-K path (N % 160 == 0, K >= 2560 in segments of 160,
+ * act 0, no row_map, no aux_out); 0 otherwise. */
+size_t dlcs_gemm_h3r_workspace_bytes(int64_t M, int64_t K, int64_t N, int act, int has_row_map, int has_aux_out);
 int dlcs_gemm_h3r(const float* A, int64_t M, int64_t K, int64_t lda, const void* bpacked, int64_t N, float* C,
                   int64_t ldc, const float* bias, int act, const float* aux, float* aux_out, int64_t ldaux, float alpha,
-                  const float* residual, int64_t ldr, const int32_t* row_map, int accumulate, dlcs_stream_t stream);
+                  const float* residual, int64_t ldr, const int32_t* row_map, int accumulate, void* workspace,
+                  size_t workspace_bytes, dlcs_stream_t stream);
 
 /* fp8 (OCP e4m3) path of the diffusion denoisers' token Linears (BASELINE config 5,
  * inference).  dlcs_f8r_quant: x fp32 [rows, K] (row stride ld, K % 4 == 0) ->
@@ -442,9 +452,12 @@ size_t dlcs_gemm_nt_x6_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int dlcs_gemm_nt_x6(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t K,
                     float* C, void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
 #endif  /* DLCS_DIAG_BUILD */
-/* dw_packed [27][160][160] (+)= fp32 weight gradient from the f16 plane pairs of x and g. */
+/* dw_packed [27][160][160] (+)= fp32 weight gradient from the f16 plane pairs of x and g.
+ * workspace: one dW partial slab per voxel range, summed in a fixed order. */
+size_t dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W);
 int dlcs_conv3d_k3_wgrad_f16x3(const void* xplanes, const void* gplanes, float* dw_packed, int64_t B, int64_t D,
-                               int64_t H, int64_t W, dlcs_stream_t stream);
+                               int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
+                               dlcs_stream_t stream);
 /* fp32 thin-end Conv3d k3 (the ConvBlocks' 2E <-> 160 ends: SFE s3d:384, final
  * layer s3d:391; replaces their fp32 nn.Conv3d calls, swin3D.py:225-273) on fp16
  * matrix cores (conv3d_thin_f16x3.inc): the fp32 activation is read once and
@@ -468,11 +481,14 @@ int dlcs_absmax_f32(const float* x, int64_t n, unsigned* out, dlcs_stream_t stre
 size_t dlcs_conv3d_thin_pack_f16x3_bytes(int kind);
 int dlcs_conv3d_thin_pack_f16x3(const float* wpacked, int64_t cout, int64_t cout_pad, int64_t cin, int64_t cin_pad,
                                 int kind, void* out, dlcs_stream_t stream);
+/* workspace: per-tile column-sum partials (0 without colsum). */
+size_t dlcs_conv3d_thin_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int has_colsum);
 int dlcs_conv3d_thin_f16x3(const float* in, int64_t cin, int64_t cin_ld, const unsigned* in_max, const void* wthin,
                            const float* bias, float* out, int64_t cout, int64_t cout_ld, int64_t B, int64_t D,
                            int64_t H, int64_t W, const float* mask, int64_t mask_ld, const float* residual,
                            int64_t res_ld, float res_scale, int accumulate, int relu_out, unsigned* out_max,
-                           void* out_planes, float* colsum, const void* mask_planes, dlcs_stream_t stream);
+                           void* out_planes, float* colsum, const void* mask_planes, void* workspace,
+                           size_t workspace_bytes, dlcs_stream_t stream);
 int dlcs_conv3d_thin_wgrad_f16x3(const float* in, int64_t cin, int64_t cin_ld, const unsigned* in_max,
                                  const float* g, int64_t cout, int64_t g_ld, const unsigned* g_max, float* dw_packed,
                                  int64_t cout_pad, int64_t cin_pad, float* colsum, int64_t B, int64_t D, int64_t H,
@@ -491,10 +507,12 @@ int dlcs_conv3d_thin_wgrad_f16x3(const float* in, int64_t cin, int64_t cin_ld, c
 int dlcs_conv3d_thin_out_planes_f16x3(const void* xplanes, const void* wthin, const float* bias, float* out,
                                       int64_t cout, int64_t cout_ld, int64_t B, int64_t D, int64_t H, int64_t W,
                                       int accumulate, int relu_out, dlcs_stream_t stream);
+/* workspace: the workgroups' partial dW slabs, summed in a fixed order. */
+size_t dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes(void);
 int dlcs_conv3d_thin_wgrad_planes_f16x3(const void* bigplanes, const float* thin, int64_t thin_ch, int64_t thin_ld,
                                         const unsigned* thin_max, int big_is_co, float* dw_packed, int64_t cout_pad,
-                                        int64_t cin_pad, int64_t B, int64_t D, int64_t H, int64_t W,
-                                        dlcs_stream_t stream);
+                                        int64_t cin_pad, int64_t B, int64_t D, int64_t H, int64_t W, void* workspace,
+                                        size_t workspace_bytes, dlcs_stream_t stream);
 /* grad [cout][cin][3][3][3] (+)= unpack(dw_packed)                           */
 int dlcs_conv3d_unpack_wgrad(const float* dw_packed, float* grad, int64_t cout, int64_t cin, int64_t cout_pad,
                              int64_t cin_pad, int accumulate, dlcs_stream_t stream);

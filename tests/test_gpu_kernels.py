@@ -1398,3 +1398,108 @@ def test_gemm_model_epilogues(case, dtype):
     if kind == "bias_gelu":
         assert nrmse((pre + bias).double().cpu().numpy(), kw["aux_out"].double().cpu().numpy()) < \
             (1e-6 if dtype == torch.float32 else 1e-2)
+
+
+def _workspace_cases(K):
+    """name -> (entry point, call, outputs): the nine entry points that take a caller
+    workspace, each through its _ops wrapper at the smallest shape that makes the
+    workspace non-zero; `call()` runs the wrapper once, writing `outputs`."""
+    g = torch.Generator(device=DEV).manual_seed(91)
+    rnd = lambda *shape, dtype=torch.float32: torch.randn(shape, device=DEV, generator=g).to(dtype)
+    bf = torch.bfloat16
+    cases = {}
+    # 272 = 256 + 16 tiles: the tail split applies (test_conv3d_f16x3_tail_split's shape)
+    tail, trows = (1, 4, 136, 128), 4 * 136 * 128
+    xt = rnd(trows, 160)
+    w = rnd(160, 160, 3, 3, 3) / (27 * 160) ** 0.5
+    pl, cs = torch.empty((K.split2(xt).numel(),), dtype=torch.uint8, device=DEV), torch.empty((160,), device=DEV)
+    cases["split2 + colsum"] = ("dlcs_split2_f16", lambda: K.split2(xt, out=pl, colsum=cs), [pl, cs])
+    gp, wd = K.split2(rnd(trows, 160)), K.conv_pack_f16x3(w, 1)
+    o1, cs1 = torch.empty((trows, 160), device=DEV), torch.empty((160,), device=DEV)
+    cases["f16x3 conv + colsum, tail split"] = (
+        "dlcs_conv3d_k3_f16x3", lambda: K.conv3d_f16x3(gp, wd, tail, mask=xt, out=o1, colsum=cs1), [o1, cs1])
+    xb, wb = xt.to(bf), K.conv_pack(w, bf, 0)
+    o2 = torch.empty((trows, 160), dtype=bf, device=DEV)
+    cases["bf16 conv 160 -> 160, tail split"] = (
+        "dlcs_conv3d_k3", lambda: K.conv3d(xb, 160, wb, 160, 160, tail, out=o2), [o2])
+    # weight gradients: four patches = four voxel ranges
+    grid, rows = (1, 4, 8, 8), 4 * 8 * 8
+    x, gr = rnd(rows, 160), rnd(rows, 160)
+    x8 = torch.zeros((rows, 8), device=DEV)
+    x8[:, :4] = rnd(rows, 4)
+    dw1 = torch.empty((27, 160, 160), device=DEV)
+    cases["bf16 wgrad 160 x 160"] = (
+        "dlcs_conv3d_k3_wgrad", lambda: K.conv3d_wgrad(x.to(bf), 160, 0, gr.to(bf), 160, grid, dw1), [dw1])
+    # one patch = one range: this kernel adds dW with float atomics, bit-repeatable only then
+    dw2, db2 = torch.empty((27, 160, 32), device=DEV), torch.empty((160,), device=DEV)
+    cases["bf16 wgrad 4 -> 160 + dbias"] = (
+        "dlcs_conv3d_k3_wgrad",
+        lambda: K.conv3d_wgrad(x8[:64].to(bf), 4, 0, gr[:64].to(bf), 160, (1, 4, 4, 4), dw2, dbias=db2), [dw2, db2])
+    px, pg = K.split2(x), K.split2(gr)
+    dw3 = torch.empty((27, 160, 160), device=DEV)
+    cases["f16x3 wgrad"] = ("dlcs_conv3d_k3_wgrad_f16x3", lambda: K.conv3d_wgrad_f16x3(px, pg, grid, dw3), [dw3])
+    ap, bp = K.split2(rnd(64, 160)), K.split2(rnd(160, 160))
+    c4, cs4 = torch.empty((64, 160), device=DEV), torch.empty((160,), device=DEV)
+    cases["K = 160 GEMM + colsum"] = (
+        "dlcs_gemm_k160_f16x3", lambda: K.gemm_k160_f16x3(ap, 64, bp, 160, c4, colsum=cs4), [c4, cs4])
+    # K = 2560: the first K (16 segments of 160) on the split-K path
+    a5 = rnd(64, 2560)
+    (wp5,) = K.h3r_pack([(rnd(160, 2560) / 2560 ** 0.5, False)])
+    c5 = torch.empty((64, 160), device=DEV)
+    cases["h3r GEMM, deep K"] = ("dlcs_gemm_h3r", lambda: K.linear_h3r(a5, wp5, 160, out=c5), [c5])
+    w4 = rnd(4, 160, 3, 3, 3) / (27 * 160) ** 0.5
+    wt = K.thin_pack_f16x3(K.conv_pack(w4, torch.float32, 1), 160, 4, 0)
+    xm = K.absmax(x8[:, :4].contiguous())
+    o6, cs6 = torch.empty((rows, 160), device=DEV), torch.empty((160,), device=DEV)
+    cases["thin f16x3 conv + colsum"] = (
+        "dlcs_conv3d_thin_f16x3",
+        lambda: K.conv3d_thin_f16x3(x8, 4, xm, wt, 160, 160, grid, mask=x, out=o6, colsum=cs6), [o6, cs6])
+    dw7 = torch.empty((27, 160, 32), device=DEV)
+    cases["thin wgrad from planes"] = (
+        "dlcs_conv3d_thin_wgrad_planes_f16x3", lambda: K.conv3d_thin_wgrad_planes(pg, x8, 4, xm, 1, grid, dw7), [dw7])
+    return cases
+
+
+def test_caller_workspaces(monkeypatch):
+    """The split kernels' partials live in a caller workspace (dlcs_*_workspace_bytes):
+    (a) one byte short is DLCS_ERR_WORKSPACE before anything is launched -- every output,
+    pre-filled with a sentinel, is untouched; (b) the workspace carries nothing into a
+    call: pre-filled with NaN or with zeros, the outputs are bit-equal."""
+    from dl_cs import _lib
+    K = _K()
+    real_ws = K._ws
+    cases = _workspace_cases(K)
+    assert len({c[0] for c in cases.values()}) == 9
+    for label, (entry, run, outs) in cases.items():
+        seen = []
+
+        def ws(byte=None, short=0):
+            def f(name, device, *size_args):
+                buf, nb = real_ws(name, device, *size_args)
+                seen.append((name, nb))
+                if byte is not None and buf is not None:
+                    buf.fill_(byte)
+                return buf, nb - short
+            return f
+
+        def sentinel():
+            for o in outs:
+                o.fill_(3)
+        # (a) one byte short
+        sentinel()
+        monkeypatch.setattr(K, "_ws", ws(short=1))
+        with pytest.raises(_lib.DlcsError, match="100003"):
+            run()
+        assert len(seen) == 1 and seen[0][0] == entry and seen[0][1] > 0, (label, seen)
+        torch.cuda.synchronize()
+        assert all(bool((o == 3).all()) for o in outs), label
+        # (b) NaN-filled vs zero-filled workspace
+        got = []
+        for byte in (0xFF, 0x00):
+            sentinel()
+            monkeypatch.setattr(K, "_ws", ws(byte=byte))
+            run()
+            got.append([o.clone() for o in outs])
+        for i, (n, z) in enumerate(zip(*got)):
+            assert torch.equal(n, z), (label, f"output {i}")
+        assert not any(bool((o == 3).all()) for o in got[0]), label

@@ -62,3 +62,34 @@ def test_product_exports_equal_header():
     out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
     exported = sorted({ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("dlcs_")})
     assert exported == declared_symbols()
+
+
+def test_workspace_queries_pair_with_entry_points():
+    """Every dlcs_<name>_workspace_bytes the header declares sizes the workspace of a
+    declared dlcs_<name> that takes `void* workspace, size_t workspace_bytes`."""
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    params = {m.group(1): " ".join(m.group(2).split())
+              for m in re.finditer(r"^[A-Za-z_][A-Za-z0-9_ ]*[ *]+(dlcs_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, re.M)}
+    queries = [n for n in params if n.endswith("_workspace_bytes")]
+    assert len(queries) >= 15
+    # one query serves several entry points of a family (dlcs_sense_*, dlcs_gemm_dw_grouped*)
+    family = {"dlcs_sense": ("dlcs_sense_fwd", "dlcs_sense_adj", "dlcs_sense_normal"),
+              "dlcs_sense_rows": ("dlcs_sense_normal_rows", "dlcs_sense_adj_rows"),
+              "dlcs_gemm_dw": ("dlcs_gemm_dw_grouped", "dlcs_gemm_dw_grouped_f32")}
+    for q in queries:
+        stem = q[:-len("_workspace_bytes")]
+        for name in family.get(stem, (stem,)):
+            assert name in params, f"{q}: no {name} declared"
+            assert "void* workspace, size_t workspace_bytes" in params[name], name
+
+
+def test_library_source_does_not_allocate_or_synchronise():
+    """dlcs.h's contract: no allocation and no host synchronisation inside the library."""
+    csrc = os.path.join(REPO, "dl-swin-gan_amd", "csrc")
+    banned = ("hipMalloc(", "hipFree(", "hipStreamSynchronize(", "hipDeviceSynchronize(")
+    for root, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".hip", ".inc", ".h")):
+                src = open(os.path.join(root, f)).read()
+                for b in banned:
+                    assert b not in src, f"{f}: {b}"
