@@ -162,8 +162,9 @@ int dlcs_window_index(int64_t B, int64_t D, int64_t H, int64_t W, int64_t wd, in
 int dlcs_gather_rows(int src_dtype, int dst_dtype, const void* src, const int32_t* idx, void* dst,
                      int64_t nrows, int64_t C, int64_t ld_src, int64_t ld_dst, dlcs_stream_t stream);
 
-/* nn.LayerNorm(C, eps=1e-5) over rows (vst:205, :211, fp32 statistics); row r
- * reads x[src_map[r]] (NULL = identity; -1 = zero pad row, vst:225).        */
+/* nn.LayerNorm(C, eps) over rows (vst:205, :211, fp32 statistics), C <= 512
+ * (else DLCS_ERR_INVALID_ARG); row r reads x[src_map[r]] (NULL = identity;
+ * -1 = zero pad row, vst:225: out row, mean and rstd written as 0).          */
 int dlcs_layernorm_fwd(int out_dtype, const float* x, const int32_t* src_map, const float* gamma,
                        const float* beta, float eps, void* out, float* mean, float* rstd,
                        int64_t rows, int64_t C, dlcs_stream_t stream);
@@ -531,7 +532,7 @@ int dlcs_swin_post_bwd(int dtype, const void* gout, void* go, int64_t B, int64_t
                        int64_t pad, int64_t ldc, dlcs_stream_t stream);
 
 /* Elementwise / layout helpers.
- *   axpby:   y = a x + b y  (dtype conversion allowed)
+ *   axpby:   y = a x + b y  (dtype conversion allowed; with b == 0 y is not read)
  *   permute: dst (shape dst_shape, contiguous) [i] (+)= src[sum_k i_k * src_strides[k]], ndim <= 6
  *   fill_bias: out[r, c] = bias[c % period] (or 0)
  *   relu_grad: g[i] = (a[i] > 0) ? g[i] : 0, in place (a = stored post-ReLU activation) */
@@ -600,7 +601,8 @@ int dlcs_mhsa_bwd(int dtype, const void* qkv, const void* out, const void* dout,
  *   im2col: dst[v][tap*C + c] = src[v + sign*off(tap)][c] (0 outside the grid), columns
  *           [27 C, ld_dst) zeroed;  off(tap) = (kd-1, kh-1, kw-1), tap = 9 kd + 3 kh + kw
  *   col2im: out[v][c] (+)= bias[c] + sum_tap P[v + sign*off(tap)][tap*C + c] for c < C
- *           (columns [C, ld_out) zeroed unless accumulate).                          */
+ *           (columns [C, ld_out) zeroed unless accumulate).
+ *   C <= 8.  D, H, W not multiples of 4: DLCS_ERR_UNSUPPORTED_SIZE, nothing written.  */
 int dlcs_conv3d_thin_im2col(const float* src, int64_t ld_src, int64_t C, float* dst, int64_t ld_dst, int sign,
                             int64_t B, int64_t D, int64_t H, int64_t W, dlcs_stream_t stream);
 int dlcs_conv3d_thin_col2im(const float* P, int64_t ld_p, int64_t C, float* out, int64_t ld_out, const float* bias,
@@ -611,13 +613,15 @@ int dlcs_conv3d_thin_col2im(const float* P, int64_t ld_p, int64_t C, float* out,
  *   dlcs_dit_vec op 0: y = SiLU(a); 1: y = a * SiLU'(b); 2: y = 1 + a (modulate's
  *     1 + scale, dit:22-23); 3: y = a + b.   (y may alias a or b)
  *   dlcs_timestep_embedding: out [B, dim] = [cos(t f_k), sin(t f_k)],
- *     f_k = exp(-ln(max_period) k / (dim/2)) (dit:198-216); t fp32 [B].
+ *     f_k = exp(-ln(max_period) k / (dim/2)) (dit:198-216); t fp32 [B]; with an odd
+ *     dim the last column is 0.
  *   dlcs_scale_rows: Wo[n,:] = gate[n] W[n,:], bo[n] = gate[n] b[n] -- a gated
- *     residual branch g * (x W^T + b) (dit:338, :345, :348) as one Linear.
+ *     residual branch g * (x W^T + b) (dit:338, :345, :348) as one Linear; b NULL:
+ *     bo is not written.
  *   dlcs_gated_linear_grad: its parameter gradients from G = dy^T x and colsum(dy):
  *     dW[n,:] += g[n] G[n,:], db[n] += g[n] cs[n], dgate[n] += W[n,:].G[n,:] + b[n] cs[n].
- *   dlcs_rows_add: dst[idx[r], :] += src[r, :] (atomic; idx NULL = identity) -- the
- *     embedding_table gradient (dit:250).                                         */
+ *   dlcs_rows_add: dst[idx[r], :] += src[r, :] (atomic; idx NULL = identity; rows with
+ *     idx[r] < 0 are skipped) -- the embedding_table gradient (dit:250).          */
 int dlcs_dit_vec(int op, const float* a, const float* b, float* y, int64_t n, dlcs_stream_t stream);
 int dlcs_timestep_embedding(const float* t, int64_t B, int64_t dim, float max_period, float* out,
                             dlcs_stream_t stream);
