@@ -19,60 +19,18 @@
 // wgrad kernel: dW[tap][co][ci] += sum_v g[v][co] * act(x)[v + off(tap)][ci],
 // one workgroup per (tap, voxel range), one wave per 32-row co tile, operands
 // staged transposed (voxel-contiguous) in LDS, fp32 atomics per workgroup tile.
-#include "dlcs_common.h"
-
+// This unit: the generic, bf16 and plain fp32 kernels, the weight pack / unpack and (DIAG
+// build) the superseded kernels; the fp32 convs on fp16 matrix cores: conv3d_f16x3.hip.
+#include "conv3d_common.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
-
-// Caller workspaces (the producers' column-sum partials, the split-K / tail / slab
-// partials of the split kernels): each size decision below is one host function that
-// both the entry point's dlcs_*_workspace_bytes query and its launch call.  A size that
-// a per-launch test hook or a DIAG knob can change is the largest over its settings.
-inline size_t ws_align(size_t n) { return (n + 255) & ~(size_t)255; }          // sub-buffers at 256-B offsets
-inline bool ws_ok(const void* ws, size_t have, size_t need) { return need == 0 || (ws && have >= need); }
-
-// 4 x 8 x 8 output tiles (1 x 2 x 2 patches) of the 160-channel conv kernels
-inline long conv_tiles(long B, long D, long H, long W) { return B * (D / 4) * ((H / 4 + 1) / 2) * ((W / 4 + 1) / 2); }
-// tiles of the last partial round of 256 workgroups that run as 5 single-chunk
-// workgroups each (the tail split of the f16x3, v6 and v7 kernels), 0 = no split
-inline unsigned conv_tail_tiles(long ntile) {
-    const long ntail = ntile % 256;
-    return ntile > ntail && ntail > 0 && ntail * 5 <= 256 ? (unsigned)ntail : 0u;
-}
-// the tail split's partial tiles: [ntail][5][256][160] floats (v7: twice the units of 80 channels)
-inline size_t conv_tail_bytes(long ntile) { return (size_t)conv_tail_tiles(ntile) * 5 * 256 * 160 * sizeof(float); }
-
-// a weight gradient's voxel ranges: nr non-empty ranges of pp patches, nr <= want
-struct PatchRanges { int nr; long pp; };
-inline PatchRanges patch_ranges(long npatch, long want) {
-    const long n0 = std::max<long>(1, std::min<long>(want, npatch));
-    const long pp = (npatch + n0 - 1) / n0;
-    return {(int)((npatch + pp - 1) / std::max<long>(1, pp)), pp};
-}
-constexpr size_t kWgSlabBytes = (size_t)27 * 160 * 160 * sizeof(float);         // one range's dW partial
-
-constexpr int kHaloT = 6, kHaloY = 10, kHaloX = 10;
-constexpr int kHalo = kHaloT * kHaloY * kHaloX;     // 600 voxels
-constexpr int CK = 32;                              // channel chunk (K per tap step)
+__device__ uint4 g_wg_zero_row[160 / 8];   // this unit's zero source row (halo voxels off the grid)
 
 template <typename T> struct ConvPad;
 template <> struct ConvPad<bf16> { static constexpr int v = 8; };
 template <> struct ConvPad<float> { static constexpr int v = 4; };
-
-DLCS_DEV long brow(int b, int t, int y, int x, int nT, int nY, int nX) {
-    const long patch = (((long)b * nT + (t >> 2)) * nY + (y >> 2)) * nX + (x >> 2);
-    return patch * 64 + ((t & 3) << 4) + ((y & 3) << 2) + (x & 3);
-}
-
-struct ConvArgs {
-    const void* in; const void* w; const float* bias; void* out;
-    const void* mask; const void* res;
-    int B, D, H, W, Cin, cin_ld, cin_pad, Cout, cout_pad, cout_ld;
-    int mask_ld, res_ld, relu_in, out_f32, res_f32, accumulate, relu_out;
-    float res_scale;
-};
 
 template <typename T>
 DLCS_DEV Frag8<T> relu8(Frag8<T> f) {
@@ -231,7 +189,12 @@ __global__ void __launch_bounds__(256) conv3d_k3_kernel(ConvArgs a) {
     }
 }
 
-// ---------------------------------------------------------------- forward / dgrad v2 (bf16)
+DLCS_DEV void mfma16(f32x4_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+}
+
+#ifdef DLCS_DIAG_BUILD
+// ---------------------------------------------------------------- forward / dgrad v2 (bf16, DIAG build: DLCS_CONV_V2=1)
 // 512 threads = 8 waves; workgroup tile = 1x2x2 patches (256 voxels) x 160
 // output channels.  Wave w: patch (w & 3) x output-channel half (w >> 2, 80 =
 // 5 x 16), v_mfma_f32_16x16x32_bf16, 4 M-tiles x 5 N-tiles per wave.  K is
@@ -239,22 +202,7 @@ __global__ void __launch_bounds__(256) conv3d_k3_kernel(ConvArgs a) {
 // into registers 6 steps ahead) x 9 steps of 3 taps (kd, kh fixed, kw = 0..2):
 // one barrier per 3 taps (60 MFMAs per wave), the next step's 3 weight slices
 // register-prefetched while the current step computes.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-DLCS_DEV void mfma16(f32x4_t& acc, const bf16x8_t& a, const bf16x8_t& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-}
-
-struct ConvV2Args {
-    const bf16* in; const bf16* w; const float* bias; void* out;
-    const bf16* mask; const void* res;
-    int B, D, H, W, cin_ld, cin_pad;
-    int cout_ld, mask_ld, res_ld, out_f32, res_f32, accumulate, relu_out;
-    float res_scale;
-    int xcd_major;          // v5: number tiles XCD-major (neighbouring halos in one L2)
-};
-
+//
 // Epilogue of a 256-voxel x 160-channel tile held by 8 waves as acc[4][5]
 // (wave: voxel quarter pw = patch of the 1x2x2 tile, channel half nh; C/D
 // rows = voxels, cols = channels).  The fp32 tile goes through LDS (Es, >=
@@ -481,6 +429,7 @@ __global__ void __launch_bounds__(512) conv3d_k3_v2_kernel(ConvV2Args a) {
     // ---- epilogue (shares the LDS of the main loop)
     conv_epilogue_256x160<2>(a, acc, reinterpret_cast<float*>(Hs), pw, nh, lane, b, pt, tyy * 2, txx * 2, nT, nY, nX);
 }
+#endif  // DLCS_DIAG_BUILD
 
 // ---------------------------------------------------------------- forward / dgrad, thin input (bf16)
 // Cin <= 4 -> 160: the SFE conv (s3d:384) and the dgrad of the final conv
@@ -493,7 +442,6 @@ __global__ void __launch_bounds__(512) conv3d_k3_v2_kernel(ConvV2Args a) {
 template <int EPI, int NTHR, int NCO, int NPASS>
 DLCS_DEV void conv_epilogue_spec(const ConvV2Args& a, const f32x4_t (&acc)[4][5], float* Es, int pw, int cw0,
                                  int co0, int lane, int b, int pt, int pyq, int pxq, int nT, int nY, int nX);
-extern __device__ uint4 g_wg_zero_row[];
 
 // The next tile's halo is register-prefetched (pointer-selected zero row for
 // off-grid voxels: no guarded loads) while the current tile runs its MFMAs and
@@ -688,12 +636,6 @@ __global__ void __launch_bounds__(448) conv3d_thin_out_kernel(ConvArgs a, int np
 }
 
 // ---------------------------------------------------------------- wgrad
-struct WgradArgs {
-    const void* in; const void* g; float* dw;
-    int B, D, H, W, Cin, cin_ld, cin_pad, Cout, g_ld, cout_pad, relu_in;
-    long vox_per_block;
-    float* dbias;           // optional: += column sums of g (the conv bias gradient)
-};
 
 template <typename T, int NT>
 __global__ void __launch_bounds__(320) conv3d_wgrad_kernel(WgradArgs a) {
@@ -787,7 +729,6 @@ __global__ void __launch_bounds__(320) conv3d_wgrad_kernel(WgradArgs a) {
 // back voxel-contiguous with ds_read_b64_tr_b16 (lane = channel, 4 voxels per
 // read) as the MFMA operands -- no scattered transposing writes.  Row stride
 // 160 / 32 bf16 (80 / 16 dwords) keeps the transposed reads conflict-free.
-typedef short v4s __attribute__((ext_vector_type(4)));
 
 DLCS_DEV Frag8<bf16> tr_frag(const bf16* base, int ld, int lane) {
     // lane l: 16-lane group g = l>>4 covers channels 16*(g&1)..+15 and voxels 8*(g>>1)..+7
@@ -924,55 +865,7 @@ __global__ void __launch_bounds__(320) conv3d_wgrad_tr_kernel(WgradArgs a, int n
 // 9 loads of a patch are L2 hits.
 constexpr int kWgC = 160;
 constexpr int kWgRows = 64 + 96;                       // g rows + halo rows per patch
-constexpr int kWgChunks = kWgRows * kWgC / 8;          // 3200 16-B chunks
 constexpr int kWgBuf = kWgRows * kWgC;                 // bf16 per LDS buffer (51200 B)
-constexpr int kWgRangesPerXcd = 3;                     // 27 of the XCD's 32 CUs busy
-
-__device__ uint4 g_wg_zero_row[kWgC / 8];  // zero source rows (halo voxels off the grid)              // zero source for halo rows off the grid
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
-typedef __attribute__((address_space(3))) v4s lds_v4s_t;
-
-// global -> LDS DMA of 16 B per lane to (wave-uniform lds_addr) + 16 * lane.
-// Issued from inline asm on purpose: hipcc cannot tell which LDS buffer a
-// builtin DMA writes and waits vmcnt(0) before every later ds_read, which would
-// serialise the prefetch of patch p+1 with the MFMAs of patch p.  The caller
-// waits (s_waitcnt vmcnt(0)) before the barrier that publishes the buffer.
-DLCS_DEV void glds16(const void* gptr, unsigned lds_addr) {
-    // m0 is saved and restored around the DMA (the compiler may keep a value in it)
-    unsigned saved;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(saved) : "v"(gptr), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-}
-
-// the same DMA with a wave-uniform 64-bit base in SGPRs and a per-lane 32-bit
-// byte offset (the saddr form: no per-lane 64-bit address arithmetic)
-DLCS_DEV void glds16_s(const void* sbase, unsigned voff, unsigned lds_addr) {
-    unsigned saved;
-    const unsigned long long sb = (unsigned long long)(uintptr_t)sbase;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)sb);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(sb >> 32));
-    const unsigned long long sbu = ((unsigned long long)hi << 32) | lo;
-    // s_nop 4: the saddr pair may come straight from v_readfirstlane
-    // (cdna_hip_programming.md 5.7 item 2)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(saved) : "v"(voff), "s"(sbu), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-}
-
-DLCS_DEV unsigned lds_offset(const void* p) {
-    return (unsigned)(uintptr_t)((const __attribute__((address_space(3))) char*)(p));
-}
-
-DLCS_DEV bf16x8_t tr_read16(const bf16* p0, const bf16* p1) {
-    const v4s r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(const_cast<bf16*>(p0)));
-    const v4s r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(const_cast<bf16*>(p1)));
-    typedef short v8s __attribute__((ext_vector_type(8)));
-    const v8s both = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-    return __builtin_bit_cast(bf16x8_t, both);
-}
 
 // Round 5: the per-unit DMA address math (divisions of the piece index, neighbour-
 // patch arithmetic, bounds tests: ~250 VALU per patch and wave, which left the three
@@ -1163,17 +1056,6 @@ __global__ void __launch_bounds__(256) wgrad_c160_reduce_kernel(const float* par
 //    for operands the launch does not have, and every global operand load of a
 //    slice is in flight before the slice's LDS round trip (49k -> 18k cycles).
 // LDS: 2 x 38.4 KB halo + 2 x 30.7 KB weight slices = 138 KB, one workgroup per CU.
-enum { kEpiRes = 1, kEpiResF32 = 2, kEpiMask = 4, kEpiAcc = 8, kEpiOutF32 = 16, kEpiGeneric = 32 };
-
-template <int EPI>
-struct EpiFlags {
-    const ConvV2Args& a;
-    DLCS_DEV bool res() const { return (EPI & kEpiGeneric) ? a.res != nullptr : (EPI & kEpiRes); }
-    DLCS_DEV bool res_f32() const { return (EPI & kEpiGeneric) ? a.res_f32 != 0 : (EPI & kEpiResF32); }
-    DLCS_DEV bool mask() const { return (EPI & kEpiGeneric) ? a.mask != nullptr : (EPI & kEpiMask); }
-    DLCS_DEV bool accum() const { return (EPI & kEpiGeneric) ? a.accumulate != 0 : (EPI & kEpiAcc); }
-    DLCS_DEV bool out_f32() const { return (EPI & kEpiGeneric) ? a.out_f32 != 0 : (EPI & kEpiOutF32); }
-};
 
 template <int EPI, int NTHR, int NCO, int NPASS>
 DLCS_DEV void conv_epilogue_spec(const ConvV2Args& a, const f32x4_t (&acc)[4][5], float* Es, int pw, int cw0,
@@ -1610,17 +1492,18 @@ __global__ void __launch_bounds__(320) conv3d_wgrad_thin_kernel(ThinWgArgs a, in
             }
 }
 
-#include "conv3d_f32.inc"
+struct ConvV6Args {                                     // the arguments of the v6 and v7 kernels
+    ConvV2Args v;
+    int tail_base;                                      // TAIL: workgroup w computes tile tail_base + w / 5, chunk w % 5
+    float* part;                                        // TAIL: raw partial tiles [5 ntail][256][160]
+    int exp;                                            // DIAG build: DLCS_V6_EXP / DLCS_V7_EXP bits
+};
+#include "conv3d_f32.inc"                               // the .inc files do not depend on one another
 #ifdef DLCS_DIAG_BUILD
 #include "conv3d_x6.inc"                                // superseded bf16 3-plane conv (DIAG build)
 #endif
-#include "conv3d_f16x3.inc"
 #include "conv3d_v6.inc"
 #include "conv3d_v7.inc"
-#include "conv3d_thin_f16x3.inc"
-#include "conv3d_thin_planes.inc"
-#include "gemm_h3r.inc"
-#include "gemm_f8r.inc"
 
 // ---------------------------------------------------------------- weight packing
 // mode 0 (forward):  P[tap][co][ci] = W[co][ci][tap]
@@ -1655,23 +1538,7 @@ __global__ void unpack_wgrad_kernel(const float* dwp, float* grad, int Cout, int
     }
 }
 
-// DLCS_CONV_V2=1 selects the v2 forward / dgrad kernel (A/B timing only);
-// DLCS_CONV_STAMP=1 makes the v5 kernel record per-workgroup timestamps
-// (dlcs_debug_conv_stamps, tools/conv_stamps.py)
-static bool conv_v2_forced() {
-    static const bool f = [] { const char* e = dlcs_knob("DLCS_CONV_V2"); return e && e[0] == '1'; }();
-    return f;
-}
-// DLCS_CONV_V5=1 (DIAG build): the 160-channel bf16 forward / dgrad on the v5 kernel
-// (one tap row per step) instead of v6 (conv3d_v6.inc), for A/B timing
-static bool conv_v5_forced() {
-    static const bool f = [] { const char* e = dlcs_knob("DLCS_CONV_V5"); return e && e[0] == '1'; }();
-    return f;
-}
-static bool conv_stamps_on() {
-    static const bool f = [] { const char* e = dlcs_knob("DLCS_CONV_STAMP"); return e && e[0] == '1'; }();
-    return f;
-}
+static bool knob_is_1(const char* name) { const char* e = dlcs_knob(name); return e && e[0] == '1'; }
 
 template <typename T>
 size_t conv_smem(int nt) { return (size_t)(kHalo + 2 * nt * 32) * (CK + ConvPad<T>::v) * sizeof(T); }
@@ -1683,6 +1550,17 @@ inline size_t conv_k3_ws_bytes(int dtype, long cin, long cin_pad, long cout, lon
     return conv_tail_bytes(conv_tiles(B, D, H, W));
 }
 
+// the arguments of the bf16 160-output-channel kernels (xcd_major: the v5 launch sets it)
+inline ConvV2Args conv_v2_args(const ConvArgs& a) {
+    ConvV2Args v{};
+    v.in = (const bf16*)a.in; v.w = (const bf16*)a.w; v.bias = a.bias; v.out = a.out;
+    v.mask = (const bf16*)a.mask; v.res = a.res;
+    v.B = a.B; v.D = a.D; v.H = a.H; v.W = a.W; v.cin_ld = a.cin_ld; v.cin_pad = a.cin_pad;
+    v.cout_ld = a.cout_ld; v.mask_ld = a.mask_ld; v.res_ld = a.res_ld; v.out_f32 = a.out_f32;
+    v.res_f32 = a.res_f32; v.accumulate = a.accumulate; v.relu_out = a.relu_out; v.res_scale = a.res_scale;
+    return v;
+}
+
 template <typename T>
 int conv_launch(const ConvArgs& a, float* tail_ws, hipStream_t st) {
     const int nT = a.D / 4, nY = a.H / 4, nX = a.W / 4;
@@ -1690,7 +1568,6 @@ int conv_launch(const ConvArgs& a, float* tail_ws, hipStream_t st) {
     if constexpr (std::is_same<T, bf16>::value) {
         // v2 epilogue uses 16-B accesses: row strides multiple of 8 elements
         // and 16-B aligned bases (torch allocations are)
-        auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
         const bool vec_ok = a.cout_ld % 8 == 0 && al16(a.out) && (!a.mask || (a.mask_ld % 8 == 0 && al16(a.mask))) &&
                             (!a.res || (a.res_ld % 8 == 0 && al16(a.res)));
         if (a.Cout <= 4 && a.Cin == 160 && a.cin_pad == 160 && a.cin_ld % 8 == 0 && al16(a.in) && !a.relu_in &&
@@ -1701,16 +1578,8 @@ int conv_launch(const ConvArgs& a, float* tail_ws, hipStream_t st) {
         }
         if (a.cout_pad == 160 && a.Cout == 160 && !a.relu_in && a.Cin <= 4 && a.cin_ld == 8 && a.cin_pad % 4 == 0 &&
             vec_ok && al16(a.in)) {
-            ConvV2Args v{};
-            v.in = (const bf16*)a.in; v.w = (const bf16*)a.w; v.bias = a.bias; v.out = a.out;
-            v.mask = (const bf16*)a.mask; v.res = a.res;
-            v.B = a.B; v.D = a.D; v.H = a.H; v.W = a.W; v.cin_ld = a.cin_ld; v.cin_pad = a.cin_pad;
-            v.cout_ld = a.cout_ld; v.mask_ld = a.mask_ld; v.res_ld = a.res_ld; v.out_f32 = a.out_f32;
-            v.res_f32 = a.res_f32; v.accumulate = a.accumulate; v.relu_out = a.relu_out; v.res_scale = a.res_scale;
-            int epi;
-            if (!v.res && !v.mask && !v.accumulate && !v.out_f32) epi = 0;
-            else if (!v.res && v.mask && !v.accumulate && !v.out_f32) epi = kEpiMask;
-            else epi = kEpiGeneric;
+            const ConvV2Args v = conv_v2_args(a);
+            const int epi = conv_epi_code(v.res, v.mask, !v.accumulate && !v.out_f32, false);
             const dim3 g(std::min(nblk, 512u));
             if (epi == 0) hipLaunchKernelGGL(conv3d_thin_in_kernel<0>, g, dim3(512), 0, st, v, (int)nblk);
             else if (epi == kEpiMask) hipLaunchKernelGGL(conv3d_thin_in_kernel<kEpiMask>, g, dim3(512), 0, st, v, (int)nblk);
@@ -1718,15 +1587,17 @@ int conv_launch(const ConvArgs& a, float* tail_ws, hipStream_t st) {
             return dlcs_launch_status();
         }
         if (a.cout_pad == 160 && a.Cout == 160 && !a.relu_in && a.cin_ld % 8 == 0 && a.Cin == a.cin_pad && vec_ok) {
-            ConvV2Args v{};
-            v.in = (const bf16*)a.in; v.w = (const bf16*)a.w; v.bias = a.bias; v.out = a.out;
-            v.mask = (const bf16*)a.mask; v.res = a.res;
-            v.B = a.B; v.D = a.D; v.H = a.H; v.W = a.W; v.cin_ld = a.cin_ld; v.cin_pad = a.cin_pad;
-            v.cout_ld = a.cout_ld; v.mask_ld = a.mask_ld; v.res_ld = a.res_ld; v.out_f32 = a.out_f32;
-            v.res_f32 = a.res_f32; v.accumulate = a.accumulate; v.relu_out = a.relu_out; v.res_scale = a.res_scale;
-            if (conv_v2_forced()) {
+            ConvV2Args v = conv_v2_args(a);
+            // DIAG build, A/B timing: DLCS_CONV_V2=1 the v2 kernel; DLCS_CONV_V5=1 v5 (one tap row
+            // per step) instead of v6; DLCS_CONV_STAMP=1 the stamping v5 instances <E, 1>
+            static const bool v5_forced = knob_is_1("DLCS_CONV_V5");
+#ifdef DLCS_DIAG_BUILD
+            static const bool v2_forced = knob_is_1("DLCS_CONV_V2"), stamp = knob_is_1("DLCS_CONV_STAMP");
+            if (v2_forced) {
                 hipLaunchKernelGGL(conv3d_k3_v2_kernel, dim3(nblk), dim3(512), 0, st, v);
-            } else if (v.cin_pad == 160 && !conv_v5_forced()) {
+            } else
+#endif
+            if (v.cin_pad == 160 && !v5_forced) {
                 // v6; DLCS_CONV_V7=1 (test hook) runs the two-workgroups-per-CU v7 kernel
                 // (same-box A/B at parity: conv3d_v7.inc header, DESIGN round-6 item 1)
                 const char* f7 = dlcs_test_hook("DLCS_CONV_V7");
@@ -1735,16 +1606,15 @@ int conv_launch(const ConvArgs& a, float* tail_ws, hipStream_t st) {
             } else {
                 // the two production epilogues (ResSwin / DFE tail forward: bf16 residual;
                 // dgrad: ReLU mask) and one runtime-flag variant for everything else
-                int epi;
-                if (!v.res && !v.mask && !v.accumulate && !v.out_f32) epi = 0;
-                else if (v.res && !v.res_f32 && !v.mask && !v.accumulate && !v.out_f32) epi = kEpiRes;
-                else if (!v.res && v.mask && !v.accumulate && !v.out_f32) epi = kEpiMask;
-                else epi = kEpiGeneric;
-                const bool stamp = conv_stamps_on();
+                const int epi = conv_epi_code(v.res, v.mask, !v.accumulate && !v.out_f32, !v.res_f32);   // fused residual: bf16
                 static const int xcd_env = [] { const char* e = dlcs_knob("DLCS_CONV_XCD"); return e ? atoi(e) : 1; }();
                 v.xcd_major = xcd_env;
+#ifdef DLCS_DIAG_BUILD
 #define V5_LAUNCH(E) do { if (stamp) hipLaunchKernelGGL((conv3d_k3_v5_kernel<E, 1>), dim3(nblk), dim3(512), 0, st, v); \
                           else hipLaunchKernelGGL((conv3d_k3_v5_kernel<E, 0>), dim3(nblk), dim3(512), 0, st, v); } while (0)
+#else
+#define V5_LAUNCH(E) hipLaunchKernelGGL((conv3d_k3_v5_kernel<E, 0>), dim3(nblk), dim3(512), 0, st, v)
+#endif
                 if (epi == 0) V5_LAUNCH(0);
                 else if (epi == kEpiRes) V5_LAUNCH(kEpiRes);
                 else if (epi == kEpiMask) V5_LAUNCH(kEpiMask);
@@ -1755,42 +1625,34 @@ int conv_launch(const ConvArgs& a, float* tail_ws, hipStream_t st) {
         }
     }
     if constexpr (std::is_same<T, float>::value) {
-        auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
         const long rows = (long)a.B * a.D * a.H * a.W;
-        if (a.cout_pad == 160 && a.Cout == 160 && a.Cin == 160 && a.cin_pad == 160 && !a.relu_in && a.out_f32 &&
-            a.cin_ld % 4 == 0 && a.cout_ld % 4 == 0 && al16(a.in) && al16(a.out) && al16(a.w) &&
-            (!a.mask || (a.mask_ld % 4 == 0 && al16(a.mask))) && (!a.res || (a.res_f32 && a.res_ld % 4 == 0 && al16(a.res))) &&
-            (!a.bias || al16(a.bias)) && rows * a.cin_ld < (1L << 31))
+        // the fast kernels' common needs: fp32 output of the plain input, 16-B rows; their epilogue operands
+        const bool io_ok = !a.relu_in && a.out_f32 && a.cin_ld % 4 == 0 && a.cout_ld % 4 == 0 && al16(a.in) && al16(a.out);
+        const bool epi_ok = (!a.mask || (a.mask_ld % 4 == 0 && al16(a.mask))) && (!a.bias || al16(a.bias)) &&
+                            (!a.res || (a.res_f32 && a.res_ld % 4 == 0 && al16(a.res)));
+        if (a.cout_pad == 160 && a.Cout == 160 && a.Cin == 160 && a.cin_pad == 160 && io_ok && epi_ok && al16(a.w) &&
+            rows * a.cin_ld < (1L << 31))
             return conv_f32_c160_launch(a, st);
         // thin input (SFE forward, final-conv dgrad): Cin <= 4 in 16-B rows
-        if (a.cout_pad == 160 && a.Cout == 160 && a.Cin <= 4 && a.cin_pad >= 4 && !a.relu_in && a.out_f32 &&
-            a.cin_ld % 4 == 0 && a.cout_ld % 4 == 0 && al16(a.in) && al16(a.out) &&
-            (!a.mask || (a.mask_ld % 4 == 0 && al16(a.mask))) && (!a.res || (a.res_f32 && a.res_ld % 4 == 0 && al16(a.res))) &&
-            (!a.bias || al16(a.bias)) && rows * a.cout_ld < (1L << 31))
+        if (a.cout_pad == 160 && a.Cout == 160 && a.Cin <= 4 && a.cin_pad >= 4 && io_ok && epi_ok && rows * a.cout_ld < (1L << 31))
             return conv_f32_thin_launch(a, st, true);
         // thin output (final conv forward, SFE dgrad): Cout <= 4 written as one 16-B row chunk
-        if (a.Cin == 160 && a.cin_pad == 160 && a.Cout <= 4 && a.cout_ld >= 4 && !a.relu_in && a.out_f32 && !a.mask &&
-            !a.res && a.cin_ld % 4 == 0 && a.cout_ld % 4 == 0 && al16(a.in) && al16(a.out) && al16(a.w) &&
+        if (a.Cin == 160 && a.cin_pad == 160 && a.Cout <= 4 && a.cout_ld >= 4 && io_ok && !a.mask && !a.res && al16(a.w) &&
             rows * a.cin_ld < (1L << 31))
             return conv_f32_thin_launch(a, st, false);
     }
     const int nt = a.cout_pad / 32;
     const size_t sm = conv_smem<T>(nt);
-    if (nt == 5) {
-        (void)hipFuncSetAttribute((const void*)conv3d_k3_kernel<T, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        hipLaunchKernelGGL((conv3d_k3_kernel<T, 5>), dim3(nblk), dim3(256), sm, st, a);
-    } else if (nt == 1) {
-        (void)hipFuncSetAttribute((const void*)conv3d_k3_kernel<T, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        hipLaunchKernelGGL((conv3d_k3_kernel<T, 1>), dim3(nblk), dim3(256), sm, st, a);
-    } else if (nt == 2) {
-        (void)hipFuncSetAttribute((const void*)conv3d_k3_kernel<T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        hipLaunchKernelGGL((conv3d_k3_kernel<T, 2>), dim3(nblk), dim3(256), sm, st, a);
-    } else if (nt == 4) {
-        (void)hipFuncSetAttribute((const void*)conv3d_k3_kernel<T, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        hipLaunchKernelGGL((conv3d_k3_kernel<T, 4>), dim3(nblk), dim3(256), sm, st, a);
-    } else {
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    }
+    auto launch = [&](auto NT) {
+        constexpr int n = decltype(NT)::value;
+        (void)hipFuncSetAttribute((const void*)conv3d_k3_kernel<T, n>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+        hipLaunchKernelGGL((conv3d_k3_kernel<T, n>), dim3(nblk), dim3(256), sm, st, a);
+    };
+    if (nt == 5) launch(std::integral_constant<int, 5>{});
+    else if (nt == 1) launch(std::integral_constant<int, 1>{});
+    else if (nt == 2) launch(std::integral_constant<int, 2>{});
+    else if (nt == 4) launch(std::integral_constant<int, 4>{});
+    else return DLCS_ERR_UNSUPPORTED_SIZE;
     return dlcs_launch_status();
 }
 
@@ -1818,7 +1680,6 @@ int wgrad_launch<bf16>(const WgradArgs& a, float* ws, hipStream_t st, bool* bias
     if (nrange < 1) nrange = 1;
     const long ppr = (npatch + nrange - 1) / nrange;
     nrange = (int)((npatch + ppr - 1) / ppr);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (mt == 5 && nt == 5 && a.Cin == 160 && a.Cout == 160 && !a.relu_in && a.cin_ld % 8 == 0 && a.g_ld % 8 == 0 &&
         al16(a.in) && al16(a.g)) {
         const long bias_rows = ((long)(a.H / 4) * (a.W / 4) + a.W / 4 + 1) * 64;
@@ -1868,7 +1729,6 @@ template <>
 int wgrad_launch<float>(const WgradArgs& a, float* ws, hipStream_t st, bool* bias_done) {
     (void)ws;
     (void)bias_done;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (a.cout_pad == 160 && a.cin_pad == 160 && a.Cin == 160 && a.Cout == 160 && !a.relu_in && a.cin_ld % 4 == 0 &&
         a.g_ld % 4 == 0 && al16(a.in) && al16(a.g))
         return wgrad_f32_c160_launch(a, st);
@@ -1915,10 +1775,6 @@ static unsigned grid_for(long n) {
 extern "C" {
 
 #ifdef DLCS_DIAG_BUILD
-int dlcs_debug_h3_stamps(void* host, int64_t n) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_h3_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-
 int dlcs_debug_conv_stamps(void* host, int64_t n) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_conv_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
 }
@@ -2021,7 +1877,6 @@ int dlcs_conv3d_k3_x6(const void* xa, const void* xb, const void* wpacked, const
                       const float* residual, int64_t res_ld, float res_scale, int accumulate, int relu_out,
                       dlcs_stream_t stream) {
     DLCS_CHECK_ARG(xa && xb && wpacked && out && B > 0);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (D % 4 || H % 4 || W % 4 || cout_ld % 4 || !al16(xa) || !al16(xb) || !al16(wpacked) || !al16(out) ||
         (mask && (mask_ld % 4 || !al16(mask))) || (residual && (res_ld % 4 || !al16(residual))) || (bias && !al16(bias)) ||
         B * D * H * W * 320 >= (1L << 31))
@@ -2037,7 +1892,6 @@ int dlcs_conv3d_k3_x6(const void* xa, const void* xb, const void* wpacked, const
 int dlcs_conv3d_k3_wgrad_x6(const void* xa, const void* xb, const void* ga, const void* gb, float* dw_packed,
                             int64_t B, int64_t D, int64_t H, int64_t W, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(xa && xb && ga && gb && dw_packed && B > 0);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (D % 4 || H % 4 || W % 4 || !al16(xa) || !al16(xb) || !al16(ga) || !al16(gb) ||
         B * D * H * W * 320 >= (1L << 40))
         return DLCS_ERR_UNSUPPORTED_SIZE;
@@ -2047,513 +1901,6 @@ int dlcs_conv3d_k3_wgrad_x6(const void* xa, const void* xb, const void* ga, cons
     return wgrad_x6_launch(v, (hipStream_t)stream);
 }
 #endif  // DLCS_DIAG_BUILD
-
-// planes [rows][320] f16, the 256-B trailer (max |x| bits in its first word) and one
-// 640-B zero row (the weight gradient's source for halo voxels off the grid)
-size_t dlcs_split2_f16_bytes(int64_t rows) { return (size_t)rows * 640 + 256 + 640; }
-
-size_t dlcs_split2_f16_workspace_bytes(int64_t rows, int has_colsum) {
-    return has_colsum ? (size_t)split2_blocks(rows) * 160 * sizeof(float) : 0;
-}
-
-int dlcs_split2_f16(const float* x, int64_t rows, int64_t ld, void* planes, int have_max, float* colsum,
-                    void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(x && planes && rows > 0 && ld >= 160);
-    if (ld % 4 || ((uintptr_t)x & 15) || ((uintptr_t)planes & 15)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (!ws_ok(workspace, workspace_bytes, dlcs_split2_f16_workspace_bytes(rows, colsum != nullptr)))
-        return DLCS_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned* mx = (unsigned*)((char*)planes + (size_t)rows * 640);
-    if (!have_max) {
-        if (hipMemsetAsync(mx, 0, 4, st) != hipSuccess) return dlcs_launch_status();
-        hipLaunchKernelGGL(absmax_kernel, dim3(std::min(h3_grid(rows * 10), 2048u)), dim3(256), 0, st, x, (long)rows,
-                           (int)ld, mx);
-    }
-    const unsigned g = split2_blocks(rows);
-    if (colsum) {
-        float* cpart = static_cast<float*>(workspace);          // one row of 160 per block
-        hipLaunchKernelGGL(split2_f16_kernel<true>, dim3(g), dim3(256), 0, st, x, (long)rows, (int)ld,
-                           (const unsigned*)mx, (f16*)planes, cpart);
-        hipLaunchKernelGGL(colsum_parts_kernel, dim3(160), dim3(256), 0, st, (const float*)cpart, (int)g, colsum);
-    } else {
-        hipLaunchKernelGGL(split2_f16_kernel<false>, dim3(g), dim3(256), 0, st, x, (long)rows, (int)ld,
-                           (const unsigned*)mx, (f16*)planes, nullptr);
-    }
-    return dlcs_launch_status();
-}
-
-size_t dlcs_conv3d_pack_weights_f16x3_bytes(void) { return (size_t)5 * 27 * 160 * 64 * 2 + 256; }
-
-int dlcs_conv3d_pack_weights_f16x3(const float* w, int mode, void* packed, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(w && packed && (mode == 0 || mode == 1));
-    if (((uintptr_t)w & 15) || ((uintptr_t)packed & 15)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned* mx = (unsigned*)((char*)packed + (size_t)5 * 27 * 160 * 64 * 2);
-    if (hipMemsetAsync(mx, 0, 4, st) != hipSuccess) return dlcs_launch_status();
-    hipLaunchKernelGGL(absmax_kernel, dim3(h3_grid(4320L * 10)), dim3(256), 0, st, w, 4320L, 160, mx);
-    hipLaunchKernelGGL(pack_weights_f16x3_kernel, dim3(h3_grid(27L * 160 * 160)), dim3(256), 0, st, w,
-                       (const unsigned*)mx, (f16*)packed, mode);
-    return dlcs_launch_status();
-}
-
-// column-sum partials of the producers that also sum their output's columns (the
-// f16x3 convs: one row of 160 per tile; the K = 160 GEMM: per 64 x 160 tile)
-static size_t colsum_part_bytes(long nwg, bool colsum) { return colsum ? (size_t)nwg * 160 * sizeof(float) : 0; }
-static long gemm_k160_tiles(long M, long N) { return (long)cdiv(M, 64) * (N / 160); }
-
-// the column-sum partials, then (at a 256-B offset) the tail split's partial tiles
-size_t dlcs_conv3d_k3_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int has_colsum) {
-    const long ntile = conv_tiles(B, D, H, W);
-    return ws_align(colsum_part_bytes(ntile, has_colsum != 0)) + conv_tail_bytes(ntile);
-}
-
-int dlcs_conv3d_k3_f16x3(const void* xplanes, const void* wpacked, const float* bias, float* out, int64_t cout_ld,
-                         int64_t B, int64_t D, int64_t H, int64_t W, const float* mask, int64_t mask_ld,
-                         const float* residual, int64_t res_ld, float res_scale, int accumulate, int relu_out,
-                         unsigned* out_max, void* out_planes, float* colsum, const void* mask_planes,
-                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(xplanes && wpacked && B > 0 && (out || (out_planes && !accumulate)) && !(mask && mask_planes));
-    if (!out) cout_ld = 160;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const long rows = (long)B * D * H * W;
-    if (D % 4 || H % 4 || W % 4 || cout_ld % 4 || !al16(xplanes) || !al16(wpacked) || !al16(out) ||
-        (mask && (mask_ld % 4 || !al16(mask))) || (residual && (res_ld % 4 || !al16(residual))) || (bias && !al16(bias)) ||
-        rows * 320 >= (1L << 31))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    ConvH3Args v{};
-    v.xp = (const f16*)xplanes; v.wp = (const f16*)wpacked;
-    v.xmax = (const unsigned*)((const char*)xplanes + rows * 640);
-    v.wmax = (const unsigned*)((const char*)wpacked + (size_t)5 * 27 * 160 * 64 * 2);
-    v.bias = bias; v.out = out; v.mask = mask; v.res = residual;
-    v.B = (int)B; v.D = (int)D; v.H = (int)H; v.W = (int)W;
-    v.cout_ld = (int)cout_ld; v.mask_ld = (int)mask_ld; v.res_ld = (int)res_ld; v.accumulate = accumulate;
-    v.relu_out = relu_out; v.res_scale = res_scale; v.omax = out_max;
-    if (mask_planes && !al16(mask_planes)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    v.mplanes = mask_planes;
-    if (out_planes) {
-        if (cout_ld != 160 || !al16(out_planes)) return DLCS_ERR_UNSUPPORTED_SIZE;
-        v.oplanes = (f16*)out_planes;
-        v.opmax = (const unsigned*)((const char*)out_planes + rows * 640);
-    }
-#ifdef DLCS_DIAG_BUILD
-    v.stamp = conv_stamps_on() ? 1 : 0;
-    static const int h3_exp = [] { const char* e = dlcs_knob("DLCS_H3_EXP"); return e ? atoi(e) : 0; }();
-    v.exp = h3_exp;
-#endif
-    hipStream_t st = (hipStream_t)stream;
-    const long ntile = conv_tiles(B, D, H, W);
-    if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_k3_f16x3_workspace_bytes(B, D, H, W, colsum != nullptr)))
-        return DLCS_ERR_WORKSPACE;
-    if (colsum) v.cpart = static_cast<float*>(workspace);     // one row of 160 per tile
-    float* tail_ws = reinterpret_cast<float*>(static_cast<char*>(workspace) +
-                                              ws_align(colsum_part_bytes(ntile, colsum != nullptr)));
-    const int rc = conv_f16x3_launch(v, tail_ws, st);
-    if (rc || !colsum) return rc;
-    hipLaunchKernelGGL(colsum_parts_kernel, dim3(160), dim3(256), 0, st, (const float*)v.cpart, (int)ntile, colsum);
-    return dlcs_launch_status();
-}
-
-size_t dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W) {
-    return (size_t)wgh3_ranges(B * (D / 4) * (H / 4) * (W / 4), true).nr * kWgSlabBytes;
-}
-
-int dlcs_conv3d_k3_wgrad_f16x3(const void* xplanes, const void* gplanes, float* dw_packed, int64_t B, int64_t D,
-                               int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
-                               dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(xplanes && gplanes && dw_packed && B > 0);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const long rows = (long)B * D * H * W;
-    if (D % 4 || H % 4 || W % 4 || !al16(xplanes) || !al16(gplanes) || rows * 320 >= (1L << 40))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    WgradH3Args v{};
-    v.xp = (const f16*)xplanes; v.gp = (const f16*)gplanes;
-    v.xmax = (const unsigned*)((const char*)xplanes + rows * 640);
-    v.gmax = (const unsigned*)((const char*)gplanes + rows * 640);
-    v.dw = dw_packed; v.B = (int)B; v.D = (int)D; v.H = (int)H; v.W = (int)W;
-    if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(B, D, H, W)))
-        return DLCS_ERR_WORKSPACE;
-    v.part = static_cast<float*>(workspace);
-    return wgrad_f16x3_launch(v, (hipStream_t)stream);
-}
-
-size_t dlcs_gemm_k160_f16x3_workspace_bytes(int64_t M, int64_t N, int has_colsum) {
-    return colsum_part_bytes(gemm_k160_tiles(M, N), has_colsum != 0);
-}
-
-int dlcs_gemm_k160_f16x3(const void* aplanes, int64_t M, const void* bplanes, int64_t N, float* C, int64_t ldc,
-                         const float* bias, int act, float alpha, const float* residual, int64_t ldr, float res_scale,
-                         const float* residual2, int64_t ldr2, float res2_scale, int accumulate, unsigned* out_max,
-                         void* out_planes, float* colsum, const void* res_planes, const void* res2_planes,
-                         void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(aplanes && bplanes && M > 0 && N > 0 && (act == 0 || act == 3) &&
-                   (C || (out_planes && !accumulate)) && !(residual && res_planes) && !(residual2 && res2_planes));
-    if (!C) ldc = N;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (N % 160 || ldc % 4 || !al16(aplanes) || !al16(bplanes) || !al16(C) || (bias && !al16(bias)) ||
-        (residual && (ldr % 4 || !al16(residual))) || (residual2 && (ldr2 % 4 || !al16(residual2))) ||
-        M * 320 >= (1L << 40))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    GemmH3Args g{};
-    g.ap = (const f16*)aplanes; g.bp = (const f16*)bplanes;
-    g.amax = (const unsigned*)((const char*)aplanes + M * 640);
-    g.bmax = (const unsigned*)((const char*)bplanes + N * 640);
-    g.c = C; g.ldc = ldc; g.bias = bias; g.act = act; g.alpha = alpha;
-    g.res = residual; g.ldr = ldr; g.res_scale = res_scale;
-    g.res2 = residual2; g.ldr2 = ldr2; g.res2_scale = res2_scale;
-    g.accumulate = accumulate; g.M = (int)M; g.N = (int)N; g.omax = out_max;
-    const long prows = M * (N / 160);                          // rows of the [M N / 160][160] view
-    if (res_planes) {
-        if (!al16(res_planes)) return DLCS_ERR_UNSUPPORTED_SIZE;
-        g.rp = (const f16*)res_planes;
-        g.rpmax = (const unsigned*)((const char*)res_planes + prows * 640);
-    }
-    if (res2_planes) {
-        if (!al16(res2_planes)) return DLCS_ERR_UNSUPPORTED_SIZE;
-        g.rp2 = (const f16*)res2_planes;
-        g.rp2max = (const unsigned*)((const char*)res2_planes + prows * 640);
-    }
-    if (out_planes) {
-        if (ldc != N || !al16(out_planes)) return DLCS_ERR_UNSUPPORTED_SIZE;
-        g.oplanes = (f16*)out_planes;
-        g.opmax = (const unsigned*)((const char*)out_planes + M * (N / 160) * 640);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const long nwg = gemm_k160_tiles(M, N);
-    if (colsum) {
-        if (g.row_map || nwg > (1L << 24)) return DLCS_ERR_UNSUPPORTED_SIZE;
-        if (!ws_ok(workspace, workspace_bytes, colsum_part_bytes(nwg, true))) return DLCS_ERR_WORKSPACE;
-        g.cpart = static_cast<float*>(workspace);
-    }
-    const int rc = gemm_k160_launch(g, st);
-    if (rc || !colsum) return rc;
-    hipLaunchKernelGGL(colsum_parts_kernel, dim3(160), dim3(256), 0, st, (const float*)g.cpart, (int)nwg, colsum);
-    return dlcs_launch_status();
-}
-
-int dlcs_linear_k160_f16x3(const void* xplanes, int64_t M, const void* wplanes, int64_t N, float* C, int64_t ldc,
-                           const float* bias, int act, const float* aux, float* aux_out, int64_t ldaux, float alpha,
-                           const float* residual, int64_t ldr, const int32_t* row_map, int accumulate,
-                           dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(xplanes && wplanes && C && M > 0 && N > 0 && act >= 0 && act <= 3 && (act != 2 || aux));
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (N % 160 || ldc % 4 || !al16(xplanes) || !al16(wplanes) || !al16(C) || (bias && !al16(bias)) ||
-        (residual && (ldr % 4 || !al16(residual))) || ((aux || aux_out) && ldaux % 4) || (aux && !al16(aux)) ||
-        (aux_out && !al16(aux_out)) || M * 320 >= (1L << 40))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    GemmH3Args g{};
-    g.ap = (const f16*)xplanes; g.bp = (const f16*)wplanes;
-    g.amax = (const unsigned*)((const char*)xplanes + M * 640);
-    g.bmax = (const unsigned*)((const char*)wplanes + N * 640);
-    g.c = C; g.ldc = ldc; g.bias = bias; g.act = act; g.alpha = alpha;
-    g.res = residual; g.ldr = ldr; g.res_scale = 1.0f;
-    g.accumulate = accumulate; g.M = (int)M; g.N = (int)N;
-    g.aux = aux; g.aux_out = aux_out; g.ldaux = ldaux; g.row_map = row_map;
-    return gemm_k160_launch(g, (hipStream_t)stream);
-}
-
-size_t dlcs_h3r_pack_bytes(int64_t rows, int64_t K) {
-    return (size_t)rows * K * 4 + (size_t)rows * 4 + (size_t)rows * kH3rKSplit * 4 + 256;
-}
-
-int dlcs_h3r_pack_multi(int n, const float* const* src, const int64_t* ld, const int* trans, const int64_t* rows,
-                        const int64_t* K, void* const* dst, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(n >= 0 && (n == 0 || (src && ld && trans && rows && K && dst)));
-    for (int i0 = 0; i0 < n; i0 += kH3rPackMax) {
-        H3rPackBatch bt{};
-        const int cnt = std::min(n - i0, kH3rPackMax);
-        int64_t maxrows = 0;
-        int maxks = 1;
-        for (int j = 0; j < cnt; ++j) {
-            const int i = i0 + j;
-            DLCS_CHECK_ARG(src[i] && dst[i] && rows[i] > 0 && K[i] > 0 && K[i] % 32 == 0 && ld[i] > 0 &&
-                           ((uintptr_t)dst[i] & 15) == 0 && (trans[i] || (ld[i] % 4 == 0 && ((uintptr_t)src[i] & 15) == 0)));
-            if (rows[i] > (1 << 20) || K[i] > 16384 || rows[i] * K[i] * 4 >= (1L << 31)) return DLCS_ERR_UNSUPPORTED_SIZE;
-            H3rPackJob& jb = bt.j[j];
-            jb.src = src[i]; jb.dst = (f16*)dst[i]; jb.inv = (float*)((char*)dst[i] + rows[i] * K[i] * 4);
-            jb.part = jb.inv + rows[i];
-            jb.rows = (int)rows[i]; jb.K = (int)K[i]; jb.ld = (int)ld[i]; jb.trans = trans[i];
-            // K splits: at least 4 chunks of 32 per split (one per wave), at most kH3rKSplit --
-            // the packing is latency-bound (16 splits of K = 10240 ran 52 us on 96 workgroups)
-            jb.nks = (int)std::max<int64_t>(1, std::min<int64_t>(kH3rKSplit, K[i] / 128));
-            maxrows = std::max(maxrows, rows[i]);
-            maxks = std::max(maxks, jb.nks);
-        }
-        const dim3 grid((unsigned)cdiv(maxrows, 64), (unsigned)cnt, (unsigned)maxks);
-        hipLaunchKernelGGL(h3r_rowmax_kernel, grid, dim3(256), 0, (hipStream_t)stream, bt);
-        hipLaunchKernelGGL(h3r_pack_kernel, grid, dim3(256), 0, (hipStream_t)stream, bt);
-        const int st = dlcs_launch_status();
-        if (st) return st;
-    }
-    return 0;
-}
-
-// deep K with a plain epilogue runs split over K: at most 8 raw partial tiles [M][N]
-static bool h3r_deep_k(long K, long N, int act, bool row_map, bool aux_out) {
-    return N % 160 == 0 && K % 160 == 0 && K / 160 >= 16 && act == 0 && !row_map && !aux_out;
-}
-
-size_t dlcs_gemm_h3r_workspace_bytes(int64_t M, int64_t K, int64_t N, int act, int has_row_map, int has_aux_out) {
-    return h3r_deep_k(K, N, act, has_row_map != 0, has_aux_out != 0) ? (size_t)8 * M * N * sizeof(float) : 0;
-}
-
-int dlcs_gemm_h3r(const float* A, int64_t M, int64_t K, int64_t lda, const void* bpacked, int64_t N, float* C,
-                  int64_t ldc, const float* bias, int act, const float* aux, float* aux_out, int64_t ldaux, float alpha,
-                  const float* residual, int64_t ldr, const int32_t* row_map, int accumulate, void* workspace,
-                  size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(A && bpacked && C && M > 0 && N > 0 && K > 0 && act >= 0 && act <= 7 &&
-                   ((act != 2 && act != 5 && act != 6) || aux) && lda >= K);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    // tile shape: N % 160 (the Swin Linears, the unembed input gradient) with K in
-    // segments of 160, else N tiles of 128 or 64 with K in segments of 192, 128 or 64
-    int nj = 0, nch = 0;
-    if (N % 160 == 0 && K % 160 == 0) { nj = 5; nch = 5; }
-    else if (N % 64 == 0 && K % 64 == 0) { nj = N % 128 == 0 ? 4 : 2; nch = K % 192 == 0 ? 6 : K % 128 == 0 ? 4 : 2; }
-    if (!nj || lda % 4 || ldc % 4 || !al16(A) || !al16(bpacked) || !al16(C) || (bias && !al16(bias)) ||
-        (residual && (ldr % 4 || !al16(residual))) || ((aux || aux_out) && ldaux % 4) || (aux && !al16(aux)) ||
-        (aux_out && !al16(aux_out)) || M >= (1L << 31) || K > 16384 || N * K * 4 >= (1L << 31))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (!ws_ok(workspace, workspace_bytes,
-               dlcs_gemm_h3r_workspace_bytes(M, K, N, act, row_map != nullptr, aux_out != nullptr)))
-        return DLCS_ERR_WORKSPACE;
-    GemmH3rArgs g{};
-    g.a = A; g.lda = lda; g.M = (int)M;
-    g.bp = (const f16*)bpacked; g.binv = (const float*)((const char*)bpacked + N * K * 4); g.N = (int)N;
-    g.c = C; g.ldc = ldc; g.bias = bias; g.act = act; g.alpha = alpha;
-    g.res = residual; g.ldr = ldr; g.row_map = row_map; g.accumulate = accumulate;
-    g.aux = aux; g.aux_out = aux_out; g.ldaux = ldaux;
-    g.ntn = (int)(N / (32 * nj));
-    g.ntiles = (int)cdiv(M, 64) * g.ntn;
-    g.nseg = (int)(K / (32 * nch));
-    hipStream_t st = (hipStream_t)stream;
-    // deep K with a plain epilogue (the unembed input gradient and patch-embed forward,
-    // K = 10240 in 64 segments of 160 on 210 row tiles): ksplit K ranges on disjoint
-    // XCD groups (8: each XCD streams its own 0.8 MB of B from its L2), raw partial
-    // tiles summed in a fixed order by h3r_ksplit_reduce_kernel.  tools/embed_bench.py:
-    // 272 us unsplit, 238 / 250 / 235 us at 2 / 4 / 8 ranges (x6 NT GEMM: 290 us)
-    g.ksplit = 1;
-    if (h3r_deep_k(K, N, act, row_map != nullptr, aux_out != nullptr)) {
-        static const int ks_env = [] { const char* e = dlcs_knob("DLCS_H3R_KSPLIT"); return e ? atoi(e) : 0; }();
-        const int ks = ks_env == 1 || ks_env == 2 || ks_env == 4 || ks_env == 8 ? ks_env : 8;
-        if (ks > 1) {
-            g.part = static_cast<float*>(workspace);    // ks <= 8 partial tiles
-            g.ksplit = ks;
-        }
-    }
-    g.per_xcd = (int)cdiv(g.ntiles, 8 / g.ksplit);
-    const dim3 grid((unsigned)(8 * g.per_xcd)), block(512);
-    if (nj == 5) {
-        // K = 480 / 640 in 160-wide segments: the per-segment fold (fp32 VALU add of the
-        // segment's tile) keeps the matrix core's accumulate chain at 15 MFMAs
-        g.nseg = (int)(K / 160);
-        if (g.nseg == 1) hipLaunchKernelGGL((gemm_h3r_kernel<5, 5, false>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((gemm_h3r_kernel<5, 5, true>), grid, block, 0, st, g);
-        if (g.ksplit > 1)
-            hipLaunchKernelGGL(h3r_ksplit_reduce_kernel, dim3((unsigned)std::min<long>(2048, cdiv(M * N / 4, 256))),
-                               dim3(256), 0, st, g);
-    } else if (nj == 4) {
-        if (nch == 6) hipLaunchKernelGGL((gemm_h3r_kernel<6, 4, true>), grid, block, 0, st, g);
-        else if (nch == 4) hipLaunchKernelGGL((gemm_h3r_kernel<4, 4, true>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((gemm_h3r_kernel<2, 4, true>), grid, block, 0, st, g);
-    } else {
-        if (nch == 6) hipLaunchKernelGGL((gemm_h3r_kernel<6, 2, true>), grid, block, 0, st, g);
-        else if (nch == 4) hipLaunchKernelGGL((gemm_h3r_kernel<4, 2, true>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((gemm_h3r_kernel<2, 2, true>), grid, block, 0, st, g);
-    }
-    return dlcs_launch_status();
-}
-
-int dlcs_f8r_quant(const float* x, int64_t rows, int64_t K, int64_t ld, void* q, float* inv, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(x && q && inv && rows > 0 && K > 0 && ld >= K);
-    if (K % 4 || ld % 4 || ((uintptr_t)x & 15) || ((uintptr_t)q & 3) || K > (1 << 20))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    hipLaunchKernelGGL(quant_f8r_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, (long)rows, (int)K,
-                       (long)ld, (unsigned*)q, inv);
-    return dlcs_launch_status();
-}
-
-int dlcs_gemm_f8r(const void* aq, const float* ainv, int64_t M, int64_t K, const void* bq, const float* binv,
-                  int64_t N, float* C, int64_t ldc, const float* bias, int act, float* aux_out, int64_t ldaux,
-                  float alpha, const float* residual, int64_t ldr, const int32_t* row_map, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(aq && ainv && bq && binv && C && M > 0 && N > 0 && K > 0 && (act == 0 || act == 1 || act == 4));
-    if (K % 64 || N % 64 || ((uintptr_t)aq & 15) || ((uintptr_t)bq & 15) || M * K >= (1L << 40))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    GemmF8rArgs g{};
-    g.a = (const unsigned char*)aq; g.ainv = ainv; g.M = (int)M;
-    g.b = (const unsigned char*)bq; g.binv = binv; g.N = (int)N; g.K = (int)K;
-    g.c = C; g.ldc = ldc; g.bias = bias; g.act = act; g.alpha = alpha;
-    g.res = residual; g.ldr = ldr; g.row_map = row_map; g.aux_out = aux_out; g.ldaux = ldaux;
-    hipLaunchKernelGGL(gemm_f8r_kernel, dim3(cdiv(M, 64), (unsigned)(N / 64)), dim3(256), 0, (hipStream_t)stream, g);
-    return dlcs_launch_status();
-}
-
-size_t dlcs_conv3d_thin_pack_f16x3_bytes(int kind) {
-    return (size_t)(kind == 0 ? kThinInHalfs : kThinOutHalfs) * 2 + 256;
-}
-
-int dlcs_conv3d_thin_pack_f16x3(const float* wpacked, int64_t cout, int64_t cout_pad, int64_t cin, int64_t cin_pad,
-                                int kind, void* out, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(wpacked && out && (kind == 0 || kind == 1) && cout <= cout_pad && cin <= cin_pad);
-    if (kind == 0 ? !(cout == 160 && cout_pad == 160 && cin >= 1 && cin <= 4)
-                  : !(cin == 160 && cin_pad == 160 && cout >= 1 && cout <= 4))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    if ((uintptr_t)out & 15) return DLCS_ERR_UNSUPPORTED_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    const int halfs = kind == 0 ? kThinInHalfs : kThinOutHalfs;
-    // max |w| word past the scale float (the buffer has 256 B of trailer)
-    unsigned* mx = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(out) + (size_t)halfs * 2 + 16);
-    if (hipMemsetAsync(mx, 0, 4, st) != hipSuccess) return dlcs_launch_status();
-    const long n = 27L * cout_pad * cin_pad;
-    hipLaunchKernelGGL(absmax_flat_kernel, dim3((unsigned)std::min<long>(64, (n / 4 + 255) / 256)), dim3(256), 0, st,
-                       wpacked, n, mx);
-    hipLaunchKernelGGL(pack_thin_f16x3_grid_kernel, dim3((unsigned)((halfs / 2 + 255) / 256)), dim3(256), 0, st,
-                       wpacked, (int)cout, (int)cout_pad, (int)cin, (int)cin_pad, kind, (const unsigned*)mx, (f16*)out);
-    return dlcs_launch_status();
-}
-
-int dlcs_abs_row_sum_max(const float* w, int64_t rows, int64_t row_stride, int64_t n_outer, int64_t outer_stride,
-                         int64_t inner, unsigned* out, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(w && out && rows > 0 && rows < (1L << 31) && n_outer > 0 && inner > 0 && n_outer * inner < (1L << 31));
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, 4, st) != hipSuccess) return dlcs_launch_status();
-    if (n_outer * inner > 2048)
-        hipLaunchKernelGGL(absrow_max_kernel<true>, dim3((unsigned)rows), dim3(256), 0, st, w, (int)rows,
-                           (long)row_stride, (int)n_outer, (long)outer_stride, (int)inner, out);
-    else
-        hipLaunchKernelGGL(absrow_max_kernel<false>, dim3((unsigned)std::min<int64_t>((rows + 3) / 4, 256)), dim3(256), 0, st,
-                           w, (int)rows,
-                           (long)row_stride, (int)n_outer, (long)outer_stride, (int)inner, out);
-    return dlcs_launch_status();
-}
-
-int dlcs_planes_bound(void* planes, int64_t rows, const unsigned* m0, const unsigned* n0, float c0,
-                      const unsigned* m1, const unsigned* n1, float c1, const float* vec, int64_t nvec, float cvec,
-                      dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(planes && rows > 0 && nvec >= 0 && nvec < (1L << 31) && (vec || nvec == 0));
-    if ((uintptr_t)planes & 15) return DLCS_ERR_UNSUPPORTED_SIZE;
-    hipLaunchKernelGGL(planes_bound_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
-                       (unsigned*)((char*)planes + (size_t)rows * 640), m0, n0, c0, m1, n1, c1, vec, (int)nvec, cvec);
-    return dlcs_launch_status();
-}
-
-int dlcs_absmax_f32(const float* x, int64_t n, unsigned* out, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(x && out && n >= 0);
-    if ((uintptr_t)x & 15) return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(absmax_flat_kernel, dim3(std::min(h3_grid(n / 4 + 1), 1024u)), dim3(256), 0,
-                       (hipStream_t)stream, x, (long)n, out);
-    return dlcs_launch_status();
-}
-
-size_t dlcs_conv3d_thin_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int has_colsum) {
-    return colsum_part_bytes(conv_tiles(B, D, H, W), has_colsum != 0);
-}
-
-int dlcs_conv3d_thin_f16x3(const float* in, int64_t cin, int64_t cin_ld, const unsigned* in_max, const void* wthin,
-                           const float* bias, float* out, int64_t cout, int64_t cout_ld, int64_t B, int64_t D,
-                           int64_t H, int64_t W, const float* mask, int64_t mask_ld, const float* residual,
-                           int64_t res_ld, float res_scale, int accumulate, int relu_out, unsigned* out_max,
-                           void* out_planes, float* colsum, const void* mask_planes, void* workspace,
-                           size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(in && in_max && wthin && B > 0 && (out || out_planes) && !(mask && mask_planes));
-    if (!out) cout_ld = 160;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const long rows = (long)B * D * H * W;
-    if (D % 4 || H % 4 || W % 4 || cin_ld % 4 || cout_ld % 4 || !al16(in) || !al16(out) || !al16(wthin) ||
-        (bias && !al16(bias)) || rows * std::max(cin_ld, cout_ld) >= (1L << 31) || rows / 64 >= (1L << 24))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    const bool thin_in = cin >= 1 && cin <= 4 && cout == 160;
-    const bool thin_out = cin == 160 && cout >= 1 && cout <= 4;
-    if (!thin_in && !thin_out) return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (thin_in && ((mask && (mask_ld % 4 || !al16(mask))) || (residual && (res_ld % 4 || !al16(residual)))))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (thin_out && (mask || residual || out_max || cout_ld < 4)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    ConvF32Args v{};
-    v.in = in; v.bias = bias; v.out = out; v.mask = mask; v.res = residual;
-    v.B = (int)B; v.D = (int)D; v.H = (int)H; v.W = (int)W; v.cin_ld = (int)cin_ld; v.cin_pad = (int)cin;
-    v.cout_ld = (int)cout_ld; v.mask_ld = (int)mask_ld; v.res_ld = (int)res_ld; v.accumulate = accumulate;
-    v.relu_out = relu_out; v.res_scale = res_scale; v.cout = (int)cout; v.cout_pad = (int)cout; v.omax = out_max;
-    v.mplanes = mask_planes;
-    hipStream_t st = (hipStream_t)stream;
-    if (!thin_in && (out_planes || colsum || mask_planes || !out)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (mask_planes && !al16(mask_planes)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (out_planes && (!al16(out_planes) || cout_ld != 160)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    const unsigned* opmax = out_planes ? (const unsigned*)((const char*)out_planes + rows * 640) : nullptr;
-    const long ntile = conv_tiles(B, D, H, W);
-    if (!ws_ok(workspace, workspace_bytes, colsum_part_bytes(ntile, colsum != nullptr))) return DLCS_ERR_WORKSPACE;
-    float* cpart = colsum ? static_cast<float*>(workspace) : nullptr;
-    const int rc = conv_thin_f16x3_launch(v, (const f16*)wthin, in_max, (int)cin, thin_in, st, (f16*)out_planes, opmax,
-                                          cpart);
-    if (rc || !colsum) return rc;
-    hipLaunchKernelGGL(colsum_parts_kernel, dim3(160), dim3(256), 0, st, (const float*)cpart, (int)ntile, colsum);
-    return dlcs_launch_status();
-}
-
-int dlcs_conv3d_thin_wgrad_f16x3(const float* in, int64_t cin, int64_t cin_ld, const unsigned* in_max,
-                                 const float* g, int64_t cout, int64_t g_ld, const unsigned* g_max, float* dw_packed,
-                                 int64_t cout_pad, int64_t cin_pad, float* colsum, int64_t B, int64_t D, int64_t H,
-                                 int64_t W, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(in && in_max && g && g_max && dw_packed && B > 0 && cout <= cout_pad && cin <= cin_pad);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool thin_sfe = cout == 160 && cin >= 1 && cin <= 4;
-    const bool thin_fin = cin == 160 && cout >= 1 && cout <= 4;
-    const long npatch = B * (D / 4) * (H / 4) * (W / 4);
-    if ((!thin_sfe && !thin_fin) || (colsum && !thin_sfe) || D % 4 || H % 4 || W % 4 || cin_ld % 4 || g_ld % 4 ||
-        !al16(in) || !al16(g) || npatch >= (1L << 24))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    ThinWgH3Args t{};
-    t.big = thin_sfe ? g : in;
-    t.thin = thin_sfe ? in : g;
-    t.big_max = thin_sfe ? g_max : in_max;
-    t.thin_max = thin_sfe ? in_max : g_max;
-    t.dw = dw_packed; t.colsum = colsum;
-    t.big_ld = (int)(thin_sfe ? g_ld : cin_ld); t.thin_ld = (int)(thin_sfe ? cin_ld : g_ld);
-    t.sgn = thin_sfe ? 1 : -1; t.big_is_co = thin_sfe; t.thin_ch = (int)(thin_sfe ? cin : cout);
-    t.cout_pad = (int)cout_pad; t.cin_pad = (int)cin_pad;
-    t.B = (int)B; t.D = (int)D; t.H = (int)H; t.W = (int)W;
-    const int nr = (int)std::min<long>(256, npatch);
-    const int pp = (int)((npatch + nr - 1) / nr);
-    hipLaunchKernelGGL(conv3d_wgrad_thin_f16x3_kernel, dim3(nr), dim3(512), 0, (hipStream_t)stream, t, nr, pp);
-    return dlcs_launch_status();
-}
-
-int dlcs_conv3d_thin_out_planes_f16x3(const void* xplanes, const void* wthin, const float* bias, float* out,
-                                      int64_t cout, int64_t cout_ld, int64_t B, int64_t D, int64_t H, int64_t W,
-                                      int accumulate, int relu_out, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(xplanes && wthin && out && B > 0 && cout >= 1 && cout <= 4 && cout_ld >= 4);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (D % 4 || H % 4 || W % 4 || cout_ld % 4 || !al16(xplanes) || !al16(wthin) || !al16(out))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    ConvF32Args v{};
-    v.bias = bias; v.out = out;
-    v.B = (int)B; v.D = (int)D; v.H = (int)H; v.W = (int)W;
-    v.cout_ld = (int)cout_ld; v.accumulate = accumulate; v.relu_out = relu_out; v.cout = (int)cout;
-    v.cout_pad = (int)cout;
-    return conv_thin_out_p_launch(v, (const f16*)xplanes, (const f16*)wthin, (hipStream_t)stream);
-}
-
-size_t dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes(void) { return (size_t)kTwpWG * 160 * 128 * sizeof(float); }
-
-int dlcs_conv3d_thin_wgrad_planes_f16x3(const void* bigplanes, const float* thin, int64_t thin_ch, int64_t thin_ld,
-                                        const unsigned* thin_max, int big_is_co, float* dw_packed, int64_t cout_pad,
-                                        int64_t cin_pad, int64_t B, int64_t D, int64_t H, int64_t W, void* workspace,
-                                        size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(bigplanes && thin && thin_max && dw_packed && B > 0 && thin_ch >= 1 && thin_ch <= 4 &&
-                   thin_ld >= 4);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (D % 4 || H % 4 || W % 4 || thin_ld % 4 || !al16(bigplanes) || !al16(thin) ||
-        (big_is_co ? (cout_pad < 160 || cin_pad < thin_ch) : (cin_pad < 160 || cout_pad < thin_ch)))
-        return DLCS_ERR_UNSUPPORTED_SIZE;
-    ThinWgPArgs t{};
-    t.bp = (const f16*)bigplanes; t.thin = thin; t.dw = dw_packed; t.thin_max = thin_max;
-    t.rows = (long)B * D * H * W;
-    t.thin_ld = (int)thin_ld; t.sgn = big_is_co ? 1 : -1; t.big_is_co = big_is_co ? 1 : 0; t.thin_ch = (int)thin_ch;
-    t.cout_pad = (int)cout_pad; t.cin_pad = (int)cin_pad;
-    t.B = (int)B; t.D = (int)D; t.H = (int)H; t.W = (int)W;
-    if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes()))
-        return DLCS_ERR_WORKSPACE;
-    t.part = static_cast<float*>(workspace);                 // one [160][128] slab per workgroup
-    return wgrad_thin_p_launch(t, (hipStream_t)stream);
-}
 
 int dlcs_conv3d_unpack_wgrad(const float* dw_packed, float* grad, int64_t cout, int64_t cin, int64_t cout_pad,
                              int64_t cin_pad, int accumulate, dlcs_stream_t stream) {

@@ -31,307 +31,9 @@
 // Workgroups are numbered XCD-major (block b runs on XCD b % 8; each XCD gets
 // one contiguous run of tiles), so neighbouring tiles share their halo rows in
 // the same L2.
-typedef _Float16 f16;
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_h3 __attribute__((ext_vector_type(4)));
-
-DLCS_DEV void mfma16h(f32x4_t& acc, const f16x8_t& a, const f16x8_t& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
-}
-
-// the power-of-two scale of a tensor from the bits of max|x| (see the header)
-DLCS_DEV float f16x3_scale(unsigned maxbits) {
-    const float m = __uint_as_float(maxbits);
-    if (!(m > 0.0f) || !(m < 3.0e38f)) return 1.0f;
-    int e;
-    const float f = frexpf(m, &e);                  // m = f 2^e, f in [0.5, 1)
-    int k = 14 - (f == 0.5f ? e - 1 : e);           // 14 - ceil(log2 m)
-    k = k < -100 ? -100 : (k > 100 ? 100 : k);
-    return ldexpf(1.0f, k);
-}
-
-// hi / lo planes of the 8 (4) consecutive channels c.. of row r of a split2 image
-// (split2_f16_kernel's layout: per 32-channel chunk the high plane, then the low)
-typedef _Float16 f16x4_h3 __attribute__((ext_vector_type(4)));
-// the low plane of u = s x given its high plane; a nonzero u whose planes would both
-// round to zero (|u| < 2^-25) keeps its sign in the smallest subnormal, so "x != 0"
-// (a ReLU mask read from the planes of a non-negative tensor) survives the split
-DLCS_DEV f16 plane_lo(float u, f16 h) {
-    f16 l = (f16)(u - (float)h);
-    if (u != 0.0f && h == (f16)0.0f && l == (f16)0.0f) l = u > 0.0f ? (f16)5.9604645e-8f : (f16)-5.9604645e-8f;
-    return l;
-}
-DLCS_DEV void put_planes8(f16* xp, long r, int c, const f32x4_t& v0, const f32x4_t& v1, float s) {
-    f16x8_t h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float u = (e < 4 ? v0[e] : v1[e - 4]) * s;
-        h[e] = (f16)u;
-        l[e] = plane_lo(u, h[e]);
-    }
-    f16* d = xp + r * 320 + (c >> 5) * 64 + (c & 31);
-    *reinterpret_cast<f16x8_t*>(d) = h;
-    *reinterpret_cast<f16x8_t*>(d + 32) = l;
-}
-DLCS_DEV void put_planes4(f16* xp, long r, int c, const f32x4_t& v, float s) {
-    f16x4_h3 h, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float u = v[e] * s;
-        h[e] = (f16)u;
-        l[e] = plane_lo(u, h[e]);
-    }
-    f16* d = xp + r * 320 + (c >> 5) * 64 + (c & 31);
-    *reinterpret_cast<f16x4_h3*>(d) = h;
-    *reinterpret_cast<f16x4_h3*>(d + 32) = l;
-}
-
-// (hi + lo) / s of 4 channels c.. of row r of a split2 image (rinv = 1 / s): the
-// value to 2^-22 relative (+ 2^-38 of the image's bound), hi + lo exact in fp32
-DLCS_DEV f32x4_t get_planes4(const f16* xp, long r, int c, float rinv) {
-    const f16* d = xp + r * 320 + (c >> 5) * 64 + (c & 31);
-    const f16x4_h3 h = *reinterpret_cast<const f16x4_h3*>(d), l = *reinterpret_cast<const f16x4_h3*>(d + 32);
-    f32x4_t v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = ((float)h[e] + (float)l[e]) * rinv;
-    return v;
-}
-
-// Planes written by the producing kernel (out_planes of the conv / K = 160 GEMM):
-// the scale must be known before the output exists, so it comes from an upper
-// bound B >= max|out| written into the trailer beforehand (dlcs_planes_bound:
-// B = c0 m0 n0 + c1 m1 n1 + cv max|vec|, with m the inputs' max |.| and n an
-// operator norm, the max absolute row sum of the weights: |W x + b + r| <=
-// ||W||_inf max|x| + max|b| + max|r|).  Any B >= max|out| gives the split's
-// guarantee (u = s x < 2^14, no overflow); a loose B only lowers the level below
-// which the low plane goes subnormal -- |x| >= 2^-17 B keep 22 bits and smaller
-// values an absolute error <= 2^-38 B.
-// max over rows r < R of sum_{o < no} sum_{i < ni} |w[r rs + o os + i]| -> *out (float
-// bits, zeroed before), fixed-order sums (run-to-run deterministic): rows of up to
-// 2048 elements one wave each (grid-stride), longer rows (a conv weight: 4320) a
-// workgroup each; one atomicMax per workgroup (10240 per-row atomics on one word
-// serialised to ~120 us)
-template <bool ROWBLK>
-__global__ void __launch_bounds__(256) absrow_max_kernel(const float* w, int R, long rs, int no, long os, int ni,
-                                                         unsigned* out) {
-    const int n = no * ni;
-    float best = 0.0f;
-    if (ROWBLK) {
-        const float* row = w + (long)blockIdx.x * rs;
-        float acc = 0.0f;
-        for (int k = threadIdx.x; k < n; k += 256) acc += fabsf(row[(long)(k / ni) * os + k % ni]);
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, 64);
-        __shared__ float red[4];
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        best = (red[0] + red[1]) + (red[2] + red[3]);
-    } else {
-        const int lane = threadIdx.x & 63;
-        for (int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6); r < R; r += gridDim.x * 4) {
-            const float* row = w + (long)r * rs;
-            float acc = 0.0f;
-            for (int k = lane; k < n; k += 64) acc += fabsf(row[(long)(k / ni) * os + k % ni]);
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m, 64);
-            best = fmaxf(best, acc);
-        }
-        __shared__ float redm[4];
-        if (lane == 0) redm[threadIdx.x >> 6] = best;
-        __syncthreads();
-        best = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
-    }
-    if (threadIdx.x == 0 && best > 0.0f) atomicMax(out, __float_as_uint(best));
-}
-
-// the trailer word of a split2 image <- bits of B (see above), rounded up by 2^-10
-// for the fp32 rounding of the sums; the zero row after the trailer as split2 writes it
-__global__ void __launch_bounds__(256) planes_bound_kernel(unsigned* trailer, const unsigned* m0, const unsigned* n0,
-                                                           float c0, const unsigned* m1, const unsigned* n1, float c1,
-                                                           const float* vec, int nvec, float cv) {
-    float vm = 0.0f;
-    for (int i = threadIdx.x; i < nvec; i += 256) vm = fmaxf(vm, fabsf(vec[i]));
-    __shared__ float red[256];
-    red[threadIdx.x] = vm;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + h]);
-        __syncthreads();
-    }
-    if (threadIdx.x < 40)
-        *reinterpret_cast<u32x4_h3*>(reinterpret_cast<char*>(trailer) + 256 + threadIdx.x * 16) = (u32x4_h3)0u;
-    if (threadIdx.x == 0) {
-        auto f = [](const unsigned* p) { return p ? __uint_as_float(*p) : 1.0f; };
-        float b = cv * red[0];
-        if (m0) b += c0 * f(m0) * f(n0);
-        if (m1) b += c1 * f(m1) * f(n1);
-        b *= 1.0f + 0.0009765625f;
-        *trailer = b > 0.0f ? __float_as_uint(b) : 0u;
-    }
-}
-
-// max |.| of a workgroup into *omax (float bits): one wave reduction, one LDS
-// slot per wave, and one atomicMax per workgroup -- skipped when the word
-// already holds at least this value (a plain read; the word only grows, so a
-// stale read can only cause a redundant atomic).  Thousands of workgroups
-// hammering one address with per-wave atomics cost ~0.5 ms per launch.
-// Every thread of the workgroup must call it (it holds a barrier).
-DLCS_DEV void block_max_to(unsigned* omax, float v, float* red) {
-    v = wave_max(v);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = red[0];
-        for (int i = 1; i < nw; ++i) m = fmaxf(m, red[i]);
-        if (m > 0.0f && m > __uint_as_float(__atomic_load_n(omax, __ATOMIC_RELAXED)))
-            atomicMax(omax, __float_as_uint(m));
-    }
-}
-
-DLCS_DEV int f16x3_halo_swz(int hy, int hx) { return 2 * (hy & 3) + ((hx >> 1) & 1); }
-
-static unsigned h3_grid(long n) { return (unsigned)std::min<long>((n + 255) / 256, 8192); }
-
-// max |x| over rows x 160 channels of a row-major [rows][ld] fp32 tensor, as
-// float bits (non-negative floats order as unsigned ints); *out zeroed before
-__global__ void __launch_bounds__(256) absmax_kernel(const float* x, long rows, int ld, unsigned* out) {
-    float m = 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    if (ld == 160) {                                    // contiguous: a flat float4 stream, 4 loads in flight
-        const f32x4_t* v = reinterpret_cast<const f32x4_t*>(x);
-        const long n = rows * 40;
-        long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-        for (; i + 3 * stride < n; i += 4 * stride) {
-            const f32x4_t a0 = v[i], a1 = v[i + stride], a2 = v[i + 2 * stride], a3 = v[i + 3 * stride];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                m = fmaxf(m, fmaxf(fmaxf(fabsf(a0[e]), fabsf(a1[e])), fmaxf(fabsf(a2[e]), fabsf(a3[e]))));
-        }
-        for (; i < n; i += stride) {
-            const f32x4_t a = v[i];
-            m = fmaxf(m, fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))));
-        }
-    } else {
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < rows * 40; i += stride) {
-            const unsigned r = (unsigned)(i / 40), c = (unsigned)(i % 40);
-            const f32x4_t a = *reinterpret_cast<const f32x4_t*>(x + (long)r * ld + c * 4);
-            m = fmaxf(m, fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))));
-        }
-    }
-    __shared__ float red[4];
-    block_max_to(out, m, red);
-}
-
-// x [rows][ld] fp32 (160 channels) -> XP [rows][320] f16 (per 32-channel chunk:
-// xh then xl); a thread handles 8 channels of a row per item, its channel group
-// fixed (the grid stride is a multiple of 20), four items in flight per
-// iteration (round 4's one-item loop ran at 3.5-4.8 TB/s on the 550 MB tensors).
-// CS: the column sums of x (a conv bias gradient) from the same read, per block
-// in a fixed thread order into cpart[block][160] -- summed by
-// colsum_parts_kernel in a fixed order (run-to-run deterministic; round 4's
-// per-block float atomics on 160 addresses from 8192 blocks cost ~80 us).
-// Block 0 also writes the zero row after the trailer (dlcs_split2_f16_bytes).
-constexpr int kSplit2Blocks = 2045;                 // 5 x 409: stride 523,520 = 20 x 26,176 threads
-template <bool CS>
-__global__ void __launch_bounds__(256) split2_f16_kernel(const float* x, long rows, int ld, const unsigned* maxbits,
-                                                         f16* xp, float* cpart) {
-    const float s = f16x3_scale(*maxbits);
-    if (blockIdx.x == 0 && threadIdx.x < 40)            // the zero row after the trailer
-        *reinterpret_cast<u32x4_h3*>(reinterpret_cast<char*>(xp) + rows * 640 + 256 + threadIdx.x * 16) = (u32x4_h3)0u;
-    float cs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const long stride = (long)gridDim.x * blockDim.x;
-    const long gt = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int c8 = (int)(gt % 20) * 8;
-    auto put = [&](long r, const f32x4_t& v0, const f32x4_t& v1) {
-        f16x8_t h, l;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float xv = e < 4 ? v0[e] : v1[e - 4];
-            if (CS) cs[e] += xv;
-            const float u = xv * s;
-            const f16 hv = (f16)u;
-            h[e] = hv;
-            l[e] = (f16)(u - (float)hv);
-        }
-        f16* dst = xp + r * 320 + (c8 >> 5) * 64 + (c8 & 31);
-        *reinterpret_cast<f16x8_t*>(dst) = h;
-        *reinterpret_cast<f16x8_t*>(dst + 32) = l;
-    };
-    // the stride is 20 x rs threads: this thread's rows are r0, r0 + rs, ... (no division per item)
-    const long rs = stride / 20;
-    long r = gt / 20;
-    for (; r + 3 * rs < rows; r += 4 * rs) {
-        f32x4_t v[4][2];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float* src = x + (r + u * rs) * ld + c8;
-            v[u][0] = *reinterpret_cast<const f32x4_t*>(src);
-            v[u][1] = *reinterpret_cast<const f32x4_t*>(src + 4);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) put(r + u * rs, v[u][0], v[u][1]);
-    }
-    for (; r < rows; r += rs)
-        put(r, *reinterpret_cast<const f32x4_t*>(x + r * ld + c8), *reinterpret_cast<const f32x4_t*>(x + r * ld + c8 + 4));
-    if (CS) {
-        __shared__ float part[256 * 8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) part[threadIdx.x * 8 + e] = cs[e];
-        __syncthreads();
-        if (threadIdx.x < 160) {
-            const int c = threadIdx.x, g = c >> 3;
-            const int t0 = (int)((g - (long)blockIdx.x * 256 % 20 + 20) % 20);   // first thread of group g
-            float sum = 0.0f;
-            for (int t = t0; t < 256; t += 20) sum += part[t * 8 + (c & 7)];
-            cpart[blockIdx.x * 160 + c] = sum;
-        }
-    }
-}
-
-// colsum[c] += sum over blocks of cpart[block][c], one workgroup per channel, fixed order
-__global__ void __launch_bounds__(256) colsum_parts_kernel(const float* cpart, int nblk, float* colsum) {
-    const int c = blockIdx.x;
-    float v = 0.0f;
-    for (int b = threadIdx.x; b < nblk; b += 256) v += cpart[b * 160 + c];
-    __shared__ float red[256];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) colsum[c] += red[0];
-}
-
-// workgroups of the split (one row of 160 column-sum partials each): the grid stride
-// is a multiple of 20 (each thread keeps one 8-channel group)
-static unsigned split2_blocks(long rows) {
-    return (unsigned)std::min<long>(kSplit2Blocks, std::max<long>(5, (rows * 20 + 255) / 256 / 5 * 5));
-}
-
-// weights [160][160][27] fp32 -> WP [5][27][160][64]; mode 0 (forward): rows co,
-// contracted ci, tap t; mode 1 (dgrad): rows ci, contracted co, tap 26 - t
-__global__ void pack_weights_f16x3_kernel(const float* w, const unsigned* maxbits, f16* wp, int mode) {
-    const float s = f16x3_scale(*maxbits);
-    const long n = 27L * 160 * 160;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % 160);
-        const int r = (int)((i / 160) % 160);
-        const int tap = (int)(i / (160L * 160));
-        const float u = s * (mode == 0 ? w[((long)r * 160 + c) * 27 + tap] : w[((long)c * 160 + r) * 27 + (26 - tap)]);
-        const f16 hv = (f16)u;
-        const long base = (((long)(c >> 5) * 27 + tap) * 160 + r) * 64 + (c & 31);
-        wp[base] = hv;
-        wp[base + 32] = (f16)(u - (float)hv);
-    }
-}
-
 constexpr int kH3Halo = kHalo * 64;            // f16 in the halo image (76.8 KB)
 constexpr int kH3Tap = 160 * 64;               // f16 in one tap slice (20 KB)
 constexpr int kH3Slot = 2 * kH3Tap;            // two tap slices per step
-constexpr int kH3Steps = 5 * 14;
 
 struct ConvH3Args {
     const f16* xp; const f16* wp; const unsigned* xmax; const unsigned* wmax;
@@ -384,161 +86,6 @@ __device__ unsigned long long g_h3_stamps[4096 * 73];
 //      the negations drain the matrix pipe).
 // The tap count of a step is a compile-time constant (the 13 two-tap steps and the
 // one-tap step of each chunk are separate instances).
-// Epilogue of the f16x3 conv for the two fused forms (EPI = kEpiRes: bias +
-// res_scale residual [+ ReLU-out, out_max]; EPI = kEpiMask: bias + ReLU mask
-// [+ out_max]): conv_epilogue_f32's two 80-channel LDS passes, with the residual
-// or mask of BOTH passes loaded into registers before the accumulators are staged,
-// so their HBM latency overlaps the LDS round trips instead of following them
-// (DIAG stamps: the epilogue was 28.6 k of a tile's 197 k cycles; 80 VGPRs of
-// prefetch beside the 80 accumulators once the main loop's registers are dead).
-// PREF = false (a caller short of registers): each pass's operands loaded in that pass.
-template <int EPI, int NPASS, bool PREF = true>
-DLCS_DEV void conv_epilogue_h3(const ConvF32Args& a, const f32x4_t (&acc)[4][5], float* Es, int pw, int cw0,
-                               int lane, int b, int pt, int pyq, int pxq, int nT, int nY, int nX,
-                               f16* op, const unsigned* opmax, float* cpart) {
-    const float ps = op ? f16x3_scale(*opmax) : 1.0f;
-    static_assert(EPI == kEpiRes || EPI == kEpiMask, "fused forms only");
-    constexpr int PC = 160 / NPASS, EL = PC + 4, NCH = PC / 8, PER = 256 * NCH / 512;
-    static_assert(PC % 8 == 0 && 256 * NCH % 512 == 0 && PC <= 512, "whole 8-channel chunks per thread");
-    const float* src = EPI == kEpiRes ? a.res : a.mask;
-    const int sld = EPI == kEpiRes ? a.res_ld : a.mask_ld;
-    // kEpiMask with a.mplanes: the mask tensor's planes (hi | lo != 0 <=> x > 0 for x >= 0)
-    const f16* mp = EPI == kEpiMask ? reinterpret_cast<const f16*>(a.mplanes) : nullptr;
-    f32x4_t pre[PREF ? NPASS : 1][PER][2];
-    long orows[PER];
-    bool oks[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int c = threadIdx.x + k * 512;
-        const int vl = c / NCH;
-        const int pwv = vl >> 6;
-        const int py = pyq + (pwv >> 1), px = pxq + (pwv & 1);
-        oks[k] = py < nY && px < nX;
-        orows[k] = ((((long)b * nT + pt) * nY + min(py, nY - 1)) * nX + min(px, nX - 1)) * 64 + (vl & 63);
-    }
-    auto load_pre = [&](int pass, int slot) {
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int c = threadIdx.x + k * 512;
-            const int co = pass * PC + (c % NCH) * 8;
-            if (mp) {                                       // the raw hi / lo planes, tested at use
-                const f16* q = mp + orows[k] * 320 + (co >> 5) * 64 + (co & 31);
-                pre[slot][k][0] = *reinterpret_cast<const f32x4_t*>(q);
-                pre[slot][k][1] = *reinterpret_cast<const f32x4_t*>(q + 32);
-            } else {
-                const float* sp = src + orows[k] * sld + co;
-                pre[slot][k][0] = *reinterpret_cast<const f32x4_t*>(sp);
-                pre[slot][k][1] = *reinterpret_cast<const f32x4_t*>(sp + 4);
-            }
-        }
-    };
-    if constexpr (PREF) {
-#pragma unroll
-        for (int pass = 0; pass < NPASS; ++pass) load_pre(pass, pass);
-    }
-    float vmax = 0.0f;
-#pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-        const int ps_ = PREF ? pass : 0;                  // this pass's operand slot
-        if constexpr (!PREF) load_pre(pass, 0);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const int c0 = cw0 + j * 16 - pass * PC;
-            if (c0 + 16 <= 0 || c0 >= PC) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int vl = pw * 64 + i * 16 + (lane >> 4) * 4 + r;
-                    const int cl = c0 + (lane & 15);
-                    if (cl >= 0 && cl < PC) Es[vl * EL + cl] = acc[i][j][r];
-                }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int c = threadIdx.x + k * 512;
-            const int vl = c / NCH, ch = (c % NCH) * 8;
-            const int co = pass * PC + ch;
-            if (!oks[k]) {
-                if (cpart) {                                // rows off the grid add nothing
-                    *reinterpret_cast<f32x4_t*>(Es + vl * EL + ch) = (f32x4_t)0.0f;
-                    *reinterpret_cast<f32x4_t*>(Es + vl * EL + ch + 4) = (f32x4_t)0.0f;
-                }
-                continue;
-            }
-            f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(Es + vl * EL + ch);
-            f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(Es + vl * EL + ch + 4);
-            if (a.bias) {
-                v0 += *reinterpret_cast<const f32x4_t*>(a.bias + co);
-                v1 += *reinterpret_cast<const f32x4_t*>(a.bias + co + 4);
-            }
-            if (EPI == kEpiMask && mp) {
-                // channel e of the 8: half e of the hi and lo f16x8 (dword e / 2)
-                const u32x4_h3 hb = __builtin_bit_cast(u32x4_h3, pre[ps_][k][0]);
-                const u32x4_h3 lb = __builtin_bit_cast(u32x4_h3, pre[ps_][k][1]);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const unsigned nz = ((hb[e >> 1] | lb[e >> 1]) >> (16 * (e & 1))) & 0x7fffu;   // -0 is zero
-                    if (e < 4) v0[e] = nz ? v0[e] : 0.0f;
-                    else v1[e - 4] = nz ? v1[e - 4] : 0.0f;
-                }
-            } else if (EPI == kEpiMask) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v0[e] = pre[ps_][k][0][e] > 0.0f ? v0[e] : 0.0f;
-                    v1[e] = pre[ps_][k][1][e] > 0.0f ? v1[e] : 0.0f;
-                }
-            } else {
-                v0 += a.res_scale * pre[ps_][k][0];
-                v1 += a.res_scale * pre[ps_][k][1];
-            }
-            if (a.relu_out) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v0[e] = fmaxf(v0[e], 0.0f); v1[e] = fmaxf(v1[e], 0.0f); }
-            }
-            if (a.out) {                                    // (planes-only output: no fp32 tensor)
-                float* o = a.out + orows[k] * a.cout_ld + co;
-                *reinterpret_cast<f32x4_t*>(o) = v0;
-                *reinterpret_cast<f32x4_t*>(o + 4) = v1;
-            }
-            if (op) put_planes8(op, orows[k], co, v0, v1, ps);
-            if (cpart) {                                    // the final values back into this item's own slot
-                *reinterpret_cast<f32x4_t*>(Es + vl * EL + ch) = v0;
-                *reinterpret_cast<f32x4_t*>(Es + vl * EL + ch + 4) = v1;
-            }
-            if (a.omax) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vmax = fmaxf(vmax, fmaxf(fabsf(v0[e]), fabsf(v1[e])));
-            }
-        }
-        if (cpart) {                                        // the tile's column sums of this pass, fixed order
-            constexpr int G = 512 / PC;                     // row groups: 6 (PC 80) or 16 (PC 32)
-            __syncthreads();
-            float* red = Es + 256 * EL;                     // [G][PC], past the staged tile
-            const int t = threadIdx.x;
-            if (t < G * PC) {
-                const int cc = t % PC, g = t / PC;
-                float cs = 0.0f;
-                for (int r = g; r < 256; r += G) cs += Es[r * EL + cc];
-                red[g * PC + cc] = cs;
-            }
-            __syncthreads();
-            if (t < PC) {
-                float cs = 0.0f;
-#pragma unroll
-                for (int g = 0; g < G; ++g) cs += red[g * PC + t];
-                cpart[pass * PC + t] = cs;
-            }
-        }
-        __syncthreads();
-    }
-    if (a.omax) {
-        vmax = wave_max(vmax);
-        if ((threadIdx.x & 63) == 0 && vmax > 0.0f && vmax > __uint_as_float(__atomic_load_n(a.omax, __ATOMIC_RELAXED)))
-            atomicMax(a.omax, __float_as_uint(vmax));
-    }
-}
 
 template <int EPI, int FOLD, bool TAIL = false>
 __global__ void __launch_bounds__(512) conv3d_k3_f16x3_kernel(ConvH3Args a) {
@@ -916,7 +463,7 @@ __global__ void __launch_bounds__(256) conv_f16x3_tail_reduce_kernel(ConvH3Args 
                 for (int e = 0; e < 4; ++e) v[e] = m[e] > 0.0f ? v[e] : 0.0f;
             } else if (a.mplanes) {
                 const f16* q = reinterpret_cast<const f16*>(a.mplanes) + orow * 320 + (c >> 5) * 64 + (c & 31);
-                const f16x4_h3 h = *reinterpret_cast<const f16x4_h3*>(q), l = *reinterpret_cast<const f16x4_h3*>(q + 32);
+                const f16x4_t h = *reinterpret_cast<const f16x4_t*>(q), l = *reinterpret_cast<const f16x4_t*>(q + 32);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = (h[e] != (f16)0.0f || l[e] != (f16)0.0f) ? v[e] : 0.0f;
             }
@@ -955,8 +502,7 @@ __global__ void __launch_bounds__(160) tail_colsum_kernel(ConvH3Args a, int npar
 // tail_ws: conv_tail_bytes(tiles) bytes for the tail split's partial tiles
 static int conv_f16x3_launch(const ConvH3Args& v0, float* tail_ws, hipStream_t st) {
     ConvH3Args v = v0;
-    const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
-    unsigned nblk = (unsigned)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
+    unsigned nblk = (unsigned)conv_tiles(v.B, v.D, v.H, v.W);
     // the last partial round of 256-CU waves (3360 tiles = 13 x 256 + 32 at BASELINE
     // size: 32 busy CUs for a whole tile time) runs as 5 x ntail single-chunk
     // workgroups plus a fixed-order reduce
@@ -965,11 +511,7 @@ static int conv_f16x3_launch(const ConvH3Args& v0, float* tail_ws, hipStream_t s
     const unsigned ntail = tail_split ? conv_tail_tiles(nblk) : 0u, nmain = nblk - ntail;
     const bool split = ntail > 0;
     if (split) nblk = nmain;
-    int epi;
-    if (!v.res && !v.mask && !v.mplanes && !v.accumulate) epi = 0;
-    else if (v.res && !v.mask && !v.mplanes && !v.accumulate) epi = kEpiRes;
-    else if (!v.res && (v.mask || v.mplanes) && !v.accumulate) epi = kEpiMask;
-    else epi = kEpiGeneric;
+    const int epi = conv_epi_code(v.res, v.mask || v.mplanes, !v.accumulate, true);
     if ((v.oplanes || v.cpart || v.mplanes) && epi != kEpiRes && epi != kEpiMask)
         return DLCS_ERR_UNSUPPORTED_SIZE;                                                   // fused forms only
     // DLCS_H3_FOLD (DIAG build; the modes above the kernel): r (default) random row
@@ -1056,13 +598,6 @@ struct WgradH3Args {
     float* part;                                     // [nrange][27][160][160] raw partials
     int B, D, H, W;
 };
-
-DLCS_DEV f16x8_t tr_read16h(const f16* p0, const f16* p1) {
-    return __builtin_bit_cast(f16x8_t, tr_read16(reinterpret_cast<const bf16*>(p0), reinterpret_cast<const bf16*>(p1)));
-}
-
-// byte offset of the zero row of a split2 buffer of `rows` rows (dlcs_split2_f16_bytes)
-DLCS_DEV long h3_zero_row_byte(long rows) { return rows * 640 + 256; }
 
 __global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, int nrange, int ppr) {
     __shared__ __attribute__((aligned(16))) f16 smem_wh[3 * kWhBuf];     // 153.6 KB: a 3-unit ring
@@ -1313,186 +848,5 @@ static int wgrad_f16x3_launch(const WgradH3Args& a, hipStream_t st) {
     const long pp = r.pp;
     hipLaunchKernelGGL(conv3d_wgrad_f16x3_kernel, dim3((unsigned)(9 * nr)), dim3(768), 0, st, a, nr, (int)pp);
     hipLaunchKernelGGL(wgrad_f16x3_reduce_kernel, dim3((unsigned)cdiv(27L * 160 * 40, 256)), dim3(256), 0, st, a, nr);
-    return dlcs_launch_status();
-}
-
-// ---------------------------------------------------------------- K = 160 GEMM on fp16 matrix cores (2-plane split)
-// C[m, n] (+)= alpha act(sum_k A[m, k] B[n, k] + bias[n]) + rs res[m, n] + rs2 res2[m, n]
-// for K = 160 with A and B as dlcs_split2_f16 plane pairs ([rows][320] +
-// max trailer): the k4s4 patch unembed forward and the patch embed's input
-// gradient (vst:455, :503 -- N = 64 x 160 = 10240 output columns per token,
-// 44 GFLOP each, 550 MB written).  Tile 64 x 160 (see v2 below), 3 plane
-// products per 16x16x32 f16 MFMA group, the conv kernels' conflict-free
-// 128-B-row swizzle for both operand images; epilogue staged through LDS so
-// every C / residual access is 16 B along a row.
-struct GemmH3Args {
-    const f16* ap; const f16* bp; const unsigned* amax; const unsigned* bmax;
-    float* c; long ldc;
-    const float* bias; int act; float alpha;
-    const float* res; long ldr; float res_scale;
-    const float* res2; long ldr2; float res2_scale;
-    int accumulate;
-    int M, N;
-    unsigned* omax;                                 // optional max |C| (float bits) for the next split
-    // token Linear epilogues (dlcs_linear_k160_f16x3): act 1 = GELU (pre-activation
-    // to aux_out), act 2 = times GELU'(aux); output / residual row row_map[m] (< 0: skip)
-    const float* aux; float* aux_out; long ldaux;
-    const int* row_map;
-    int xcd_nt;                                     // > 0: 1-D grid, xcd_nt consecutive N tiles per XCD
-    f16* oplanes; const unsigned* opmax;            // optional split2 image of C as [M N / 160][160] (ldc == N)
-    float* cpart;                                   // optional column-sum partials [M / 64 tiles][N / 160][160] (c % 160)
-    const f16* rp; const f16* rp2;                  // residuals as split2 images of the [M N / 160][160] view (instead of res / res2)
-    const unsigned* rpmax; const unsigned* rp2max;
-};
-// v3: 64-row tiles; the A tile's whole K (5 x 8 KB) DMA'd up front, B streamed
-// per 32-channel chunk through a 2-slot ring (2 x 20 KB): 80 KB, so two
-// workgroups share a CU and one's DMA waits / epilogue overlap the other's
-// MFMAs (v1, 128-row tiles with a one-chunk lookahead on both operands: 546 us
-// for the 44-GFLOP unembed; v2, whole K of both up front in 140 KB = one
-// workgroup per CU: no overlap).  8 waves of 16 x 80.
-constexpr int kG3A = 64 * 64, kG3B = 160 * 64;        // f16 per operand chunk (8 KB / 20 KB)
-
-__global__ void __launch_bounds__(512, 2) gemm_k160_f16x3_kernel(GemmH3Args g) {
-    __shared__ __attribute__((aligned(16))) f16 smem_g3[5 * kG3A + 2 * kG3B];   // 80 KB
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave & 3, wn = wave >> 2;
-    int mt = blockIdx.x, nt = blockIdx.y;
-    if (g.xcd_nt) {
-        // XCD x owns N tiles [x xcd_nt, (x + 1) xcd_nt) and walks the M tiles in
-        // order: its B planes (xcd_nt x 100 KB) stay in its L2 and each A tile is
-        // read by xcd_nt neighbouring workgroups (the one-tile-per-block order
-        // streamed all 6.5 MB of B through every XCD's L2 from the MALL)
-        const int k = blockIdx.x >> 3;
-        nt = (blockIdx.x & 7) * g.xcd_nt + k % g.xcd_nt;
-        mt = k / g.xcd_nt;
-    }
-    const int m0 = mt * 64, n0 = nt * 160;
-    const unsigned sbase = lds_offset(smem_g3);
-    // A: instruction wi (0..39) = chunk wi / 8, rows 8 (wi % 8) ..
-    auto issue_a = [&]() {
-        for (int wi = wave; wi < 40; wi += 8) {
-            const int cc = wi >> 3, rb = wi & 7;
-            const int r = rb * 8 + (lane >> 3), pc = lane & 7;
-            const int lc = pc ^ ((r >> 1) & 7);
-            const f16* src = g.ap + (long)min(m0 + r, g.M - 1) * 320 + cc * 64 + lc * 8;
-            glds16(src, sbase + (unsigned)(cc * kG3A * 2 + rb * 1024));
-        }
-    };
-    // B chunk cc into slot: 20 instructions, rows 8 rb ..
-    auto issue_b = [&](int cc, int slot) {
-        for (int rb = wave; rb < 20; rb += 8) {
-            const int r = rb * 8 + (lane >> 3), pc = lane & 7;
-            const int lc = pc ^ ((r >> 1) & 7);
-            const f16* src = g.bp + (long)min(n0 + r, g.N - 1) * 320 + cc * 64 + lc * 8;
-            glds16(src, sbase + (unsigned)((5 * kG3A + slot * kG3B) * 2 + rb * 1024));
-        }
-    };
-    issue_a();
-    issue_b(0, 0);
-    f32x4_t acc[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) acc[j] = (f32x4_t)0.0f;
-    const int vq = lane & 15, cq = lane >> 4, sw = (vq >> 1) & 7;
-    const int oh = (cq ^ sw) << 3, ol = ((4 + cq) ^ sw) << 3;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int cc = 0; cc < 5; ++cc) {
-        if (cc + 1 < 5) issue_b(cc + 1, (cc + 1) & 1);
-        const f16* As = smem_g3 + cc * kG3A + (wm * 16 + vq) * 64;
-        const f16* Bs = smem_g3 + 5 * kG3A + (cc & 1) * kG3B + (wn * 80 + vq) * 64;
-        const f16x8_t ah = *reinterpret_cast<const f16x8_t*>(As + oh);
-        const f16x8_t al = *reinterpret_cast<const f16x8_t*>(As + ol);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const f16x8_t bh = *reinterpret_cast<const f16x8_t*>(Bs + j * 16 * 64 + oh);
-            const f16x8_t bl = *reinterpret_cast<const f16x8_t*>(Bs + j * 16 * 64 + ol);
-            mfma16h(acc[j], ah, bh);
-            mfma16h(acc[j], ah, bl);
-            mfma16h(acc[j], al, bh);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    const float inv = 1.0f / (f16x3_scale(*g.amax) * f16x3_scale(*g.bmax));
-    __syncthreads();                                     // operand images dead: reuse LDS for the epilogue
-    float* Es = reinterpret_cast<float*>(smem_g3);       // [64][164]
-    constexpr int EL = 164;
-    const float ps = g.oplanes ? f16x3_scale(*g.opmax) : 1.0f;
-    const float rinv = g.rp ? 1.0f / f16x3_scale(*g.rpmax) : 1.0f;        // exact: powers of two
-    const float rinv2 = g.rp2 ? 1.0f / f16x3_scale(*g.rp2max) : 1.0f;
-    float vmax = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            Es[(wm * 16 + 4 * cq + r) * EL + wn * 80 + j * 16 + vq] = acc[j][r] * inv;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int c = threadIdx.x + k * 512;             // 64 rows x 40 16-B chunks
-        const int ml = c / 40, ch = (c % 40) * 4;
-        const long m = m0 + ml, n = n0 + ch;
-        if (m >= g.M || n >= g.N) {
-            if (g.cpart) *reinterpret_cast<f32x4_t*>(Es + ml * EL + ch) = (f32x4_t)0.0f;
-            continue;
-        }
-        long orow = m;
-        if (g.row_map) {
-            orow = g.row_map[m];
-            if (orow < 0) continue;
-        }
-        f32x4_t v = *reinterpret_cast<const f32x4_t*>(Es + ml * EL + ch);
-        if (g.bias) v += *reinterpret_cast<const f32x4_t*>(g.bias + n);
-        if (g.act == 3) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
-        } else if (g.act == 1) {
-            if (g.aux_out) *reinterpret_cast<f32x4_t*>(g.aux_out + m * g.ldaux + n) = v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-        } else if (g.act == 2) {
-            const f32x4_t av = *reinterpret_cast<const f32x4_t*>(g.aux + m * g.ldaux + n);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] *= gelu_erf_grad(av[e]);
-        }
-        v *= g.alpha;
-        if (g.res) v += g.res_scale * *reinterpret_cast<const f32x4_t*>(g.res + orow * g.ldr + n);
-        if (g.res2) v += g.res2_scale * *reinterpret_cast<const f32x4_t*>(g.res2 + orow * g.ldr2 + n);
-        if (g.rp) v += g.res_scale * get_planes4(g.rp, orow * (g.N / 160) + nt, ch, rinv);
-        if (g.rp2) v += g.res2_scale * get_planes4(g.rp2, orow * (g.N / 160) + nt, ch, rinv2);
-        if (g.c) {                                       // (planes-only output: no fp32 C)
-            float* cp = g.c + orow * g.ldc + n;
-            if (g.accumulate) v += *reinterpret_cast<const f32x4_t*>(cp);
-            *reinterpret_cast<f32x4_t*>(cp) = v;
-        }
-        if (g.oplanes) put_planes4(g.oplanes, orow * (g.N / 160) + nt, ch, v, ps);
-        if (g.cpart) *reinterpret_cast<f32x4_t*>(Es + ml * EL + ch) = v;   // this item's own slot
-        vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-    }
-    if (g.cpart) {                                       // the tile's column sums, fixed order
-        __syncthreads();
-        if (threadIdx.x < 160) {
-            float cs = 0.0f;
-            for (int r = 0; r < 64; ++r) cs += Es[r * EL + threadIdx.x];
-            g.cpart[((long)mt * (g.N / 160) + nt) * 160 + threadIdx.x] = cs;
-        }
-    }
-    if (g.omax) block_max_to(g.omax, vmax, Es + 64 * EL);    // past the staged tile: LDS stays at 80 KB
-}
-
-// v4 of round 5 (B planes resident in registers, A streamed through a 2-slot
-// ring, one workgroup of 4 waves per CU) moved 3.5x less global -> LDS data but ran
-// slower (unembed 273 vs 258 us, embed input gradient 821 vs 433 us): with four
-// waves a CU no longer overlaps one tile's epilogue traffic with another's MFMAs.
-static int gemm_k160_launch(const GemmH3Args& g0, hipStream_t st) {
-    GemmH3Args g = g0;
-    const int ntiles = g.N / 160;
-    if (g.xcd_nt >= 0 && ntiles % 8 == 0) {
-        g.xcd_nt = ntiles / 8;
-        hipLaunchKernelGGL(gemm_k160_f16x3_kernel, dim3(cdiv(g.M, 64) * (unsigned)ntiles), dim3(512), 0, st, g);
-    } else {
-        g.xcd_nt = 0;
-        hipLaunchKernelGGL(gemm_k160_f16x3_kernel, dim3(cdiv(g.M, 64), (unsigned)ntiles), dim3(512), 0, st, g);
-    }
     return dlcs_launch_status();
 }

@@ -2,7 +2,7 @@
 // (v_mfma_f32_16x16x4_f32: exact f32 FMA chains at the f32 peak, 157 TF on
 // MI355X -- 1/16 of bf16, so these kernels are far easier to keep fed than the
 // bf16 ones; the design goal is the MFMA issue rate with no exposed latency).
-// Included by conv3d.hip (shares its args structs, DMA helpers and layout).
+// Included by conv3d.hip (args structs and layout: conv3d_common.h; DMA helpers: lds_dma.h).
 //
 // Operand convention of v_mfma_f32_16x16x4_f32: lane l holds ONE f32 of A
 // (A[m = l & 15][k = l >> 4]) and of B (B[k = l >> 4][n = l & 15]); C/D as the
@@ -26,7 +26,6 @@
 constexpr int kWfC = 160;
 constexpr int kWfRows = 32 + 48;                      // g rows + halo rows per unit
 constexpr int kWfBuf = kWfRows * kWfC;                // floats per LDS buffer (51200 B)
-constexpr int kWfChunks = kWfRows * kWfC / 4;         // 3200 16-B chunks = 50 wave-instructions
 
 __device__ float4 g_wf_zero_row[kWfC / 4];            // zero source row (halo voxels off the grid)
 
@@ -190,102 +189,6 @@ static int wgrad_f32_c160_launch(const WgradArgs& a, hipStream_t st) {
 // contributes k = channel 4 cq + e -- A and B agree, so the 4 MFMAs sum all 16
 // channels of the chunk.  Per step 240 MFMAs (7680 cycles) per wave, two waves
 // per SIMD: 15.4k MFMA cycles per barrier.
-struct ConvF32Args {
-    const float* in; const float* w; const float* bias; float* out;
-    const float* mask; const float* res;
-    int B, D, H, W, cin_ld, cin_pad;
-    int cout_ld, mask_ld, res_ld, accumulate, relu_out;
-    float res_scale;
-    int cout, cout_pad;
-    unsigned* omax;         // optional: max |out| as float bits (atomicMax) for the next f16 split
-    const void* mplanes;    // the f16x3 fused epilogue: the ReLU mask as the split2 planes of a non-negative tensor
-};
-
-// epilogue of the 256 x 160 tile (acc[4][5] per wave, rows = voxels), staged
-// through LDS in two 80-channel passes, 16-B accesses throughout (s3d:256-259,
-// :339-340, :368, :427).  The main loop is 90 barrier steps long, so the
-// epilogue's operand loads are simply issued after the LDS round trip (no
-// register prefetch: it would spill beside the 80 accumulators).
-template <int EPI, int NPASS = 2>
-DLCS_DEV void conv_epilogue_f32(const ConvF32Args& a, const f32x4_t (&acc)[4][5], float* Es, int pw, int cw0,
-                                int lane, int b, int pt, int pyq, int pxq, int nT, int nY, int nX) {
-    constexpr int PC = 160 / NPASS, EL = PC + 4, NCH = PC / 8, PER = 256 * NCH / 512;
-    static_assert(256 * NCH % 512 == 0, "whole 8-channel chunks per thread");
-    const bool has_res = (EPI & kEpiGeneric) ? a.res != nullptr : (EPI & kEpiRes);
-    const bool has_mask = (EPI & kEpiGeneric) ? a.mask != nullptr : (EPI & kEpiMask);
-    const bool accum = (EPI & kEpiGeneric) ? a.accumulate != 0 : (EPI & kEpiAcc);
-    float vmax = 0.0f;
-#pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const int c0 = cw0 + j * 16 - pass * PC;
-            if (c0 + 16 <= 0 || c0 >= PC) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int vl = pw * 64 + i * 16 + (lane >> 4) * 4 + r;
-                    const int cl = c0 + (lane & 15);
-                    if (cl >= 0 && cl < PC) Es[vl * EL + cl] = acc[i][j][r];
-                }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int c = threadIdx.x + k * 512;
-            const int vl = c / NCH, ch = (c % NCH) * 8;
-            const int pwv = vl >> 6;
-            const int py = pyq + (pwv >> 1), px = pxq + (pwv & 1);
-            if (py >= nY || px >= nX) continue;
-            const long orow = ((((long)b * nT + pt) * nY + py) * nX + px) * 64 + (vl & 63);
-            const int co = pass * PC + ch;
-            f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(Es + vl * EL + ch);
-            f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(Es + vl * EL + ch + 4);
-            if (a.bias) {
-                v0 += *reinterpret_cast<const f32x4_t*>(a.bias + co);
-                v1 += *reinterpret_cast<const f32x4_t*>(a.bias + co + 4);
-            }
-            if (has_mask) {
-                const float* mp = a.mask + orow * a.mask_ld + co;
-                const f32x4_t m0 = *reinterpret_cast<const f32x4_t*>(mp);
-                const f32x4_t m1 = *reinterpret_cast<const f32x4_t*>(mp + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v0[e] = m0[e] > 0.0f ? v0[e] : 0.0f;
-                    v1[e] = m1[e] > 0.0f ? v1[e] : 0.0f;
-                }
-            }
-            if (has_res) {
-                const float* rp = a.res + orow * a.res_ld + co;
-                v0 += a.res_scale * *reinterpret_cast<const f32x4_t*>(rp);
-                v1 += a.res_scale * *reinterpret_cast<const f32x4_t*>(rp + 4);
-            }
-            if (a.relu_out) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v0[e] = fmaxf(v0[e], 0.0f); v1[e] = fmaxf(v1[e], 0.0f); }
-            }
-            float* o = a.out + orow * a.cout_ld + co;
-            if (accum) {
-                v0 += *reinterpret_cast<const f32x4_t*>(o);
-                v1 += *reinterpret_cast<const f32x4_t*>(o + 4);
-            }
-            *reinterpret_cast<f32x4_t*>(o) = v0;
-            *reinterpret_cast<f32x4_t*>(o + 4) = v1;
-            if (a.omax) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vmax = fmaxf(vmax, fmaxf(fabsf(v0[e]), fabsf(v1[e])));
-            }
-        }
-        __syncthreads();
-    }
-    if (a.omax) {
-        vmax = wave_max(vmax);
-        // one atomic per wave, skipped unless it raises the max (see block_max_to in conv3d_f16x3.inc)
-        if ((threadIdx.x & 63) == 0 && vmax > 0.0f && vmax > __uint_as_float(__atomic_load_n(a.omax, __ATOMIC_RELAXED)))
-            atomicMax(a.omax, __float_as_uint(vmax));
-    }
-}
 
 constexpr int kF5Slot = 3 * 160 * 16;                 // floats per weight slice (3 taps x 160 co x 16 ci)
 
@@ -439,13 +342,8 @@ static int conv_f32_c160_launch(const ConvArgs& a, hipStream_t st) {
     v.B = a.B; v.D = a.D; v.H = a.H; v.W = a.W; v.cin_ld = a.cin_ld; v.cin_pad = a.cin_pad;
     v.cout_ld = a.cout_ld; v.mask_ld = a.mask_ld; v.res_ld = a.res_ld; v.accumulate = a.accumulate;
     v.relu_out = a.relu_out; v.res_scale = a.res_scale;
-    const int nT = a.D / 4, nY = a.H / 4, nX = a.W / 4;
-    const unsigned nblk = (unsigned)((long)a.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
-    int epi;
-    if (!v.res && !v.mask && !v.accumulate) epi = 0;
-    else if (v.res && !v.mask && !v.accumulate) epi = kEpiRes;
-    else if (!v.res && v.mask && !v.accumulate) epi = kEpiMask;
-    else epi = kEpiGeneric;
+    const unsigned nblk = (unsigned)conv_tiles(a.B, a.D, a.H, a.W);
+    const int epi = conv_epi_code(v.res, v.mask, !v.accumulate, true);
     if (epi == 0) hipLaunchKernelGGL(conv3d_k3_f32_kernel<0>, dim3(nblk), dim3(512), 0, st, v);
     else if (epi == kEpiRes) hipLaunchKernelGGL(conv3d_k3_f32_kernel<kEpiRes>, dim3(nblk), dim3(512), 0, st, v);
     else if (epi == kEpiMask) hipLaunchKernelGGL(conv3d_k3_f32_kernel<kEpiMask>, dim3(nblk), dim3(512), 0, st, v);
@@ -803,14 +701,10 @@ static int conv_f32_thin_launch(const ConvArgs& a, hipStream_t st, bool thin_in)
     v.B = a.B; v.D = a.D; v.H = a.H; v.W = a.W; v.cin_ld = a.cin_ld; v.cin_pad = a.cin_pad;
     v.cout_ld = a.cout_ld; v.mask_ld = a.mask_ld; v.res_ld = a.res_ld; v.accumulate = a.accumulate;
     v.relu_out = a.relu_out; v.res_scale = a.res_scale; v.cout = a.Cout; v.cout_pad = a.cout_pad;
-    const int nT = a.D / 4, nY = a.H / 4, nX = a.W / 4;
-    const int ntiles = (int)((long)a.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
+    const int ntiles = (int)conv_tiles(a.B, a.D, a.H, a.W);
     if (thin_in) {
         const dim3 g(std::min(ntiles, 256));
-        int epi;
-        if (!v.res && !v.mask && !v.accumulate) epi = 0;
-        else if (!v.res && v.mask && !v.accumulate) epi = kEpiMask;
-        else epi = kEpiGeneric;
+        const int epi = conv_epi_code(v.res, v.mask, !v.accumulate, false);
         if (epi == 0) hipLaunchKernelGGL(conv3d_thin_in_f32_kernel<0>, g, dim3(512), 0, st, v, ntiles);
         else if (epi == kEpiMask) hipLaunchKernelGGL(conv3d_thin_in_f32_kernel<kEpiMask>, g, dim3(512), 0, st, v, ntiles);
         else hipLaunchKernelGGL(conv3d_thin_in_f32_kernel<kEpiGeneric>, g, dim3(512), 0, st, v, ntiles);

@@ -17,7 +17,6 @@
 // time at the dense peak, vs 550 MB = 69 us of HBM).
 // Weights are packed per call by pack_thin_f16x3_kernel (one workgroup: max,
 // scale, planes) from the fp32 packing of dlcs_conv3d_pack_weights.
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 
 DLCS_DEV void mfma32h(f32x16& acc, const f16x8_t& a, const f16x8_t& b) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
@@ -49,10 +48,6 @@ DLCS_DEV void split_f16(float x, float s, f16& h, f16& l) {
     h = (f16)u;
     l = (f16)(u - (float)h);
 }
-
-// packed weight images (f16 counts; the float s_w follows the planes)
-constexpr int kThinInHalfs = 2 * 4 * 4 * 160 * 8;      // [plane][ks 4][kg 4][co 160][8]
-constexpr int kThinOutHalfs = 5 * 9 * 2 * 4 * 16 * 8;  // [cc 5][kk 9][plane][kg 4][n 16][8]
 
 // Grid-wide version (dlcs_conv3d_thin_pack_f16x3): max |w| by absmax_flat_kernel into
 // the word `mx` first, then the planes by a grid of workgroups (block 0 writes s) --
@@ -135,21 +130,6 @@ __global__ void __launch_bounds__(1024) pack_thin_f16x3_kernel(const float* wp, 
         }
         if (threadIdx.x == 0) *reinterpret_cast<float*>(out + kThinOutHalfs) = s;
     }
-}
-
-// max |x| over n floats into *out (float bits; atomicMax, *out zeroed before)
-__global__ void __launch_bounds__(256) absmax_flat_kernel(const float* x, long n, unsigned* out) {
-    float m = 0.0f;
-    const long stride = (long)gridDim.x * blockDim.x;
-    const long n4 = n >> 2;
-    const f32x4_t* v = reinterpret_cast<const f32x4_t*>(x);
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const f32x4_t a = v[i];
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))));
-    }
-    for (long i = n4 * 4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) m = fmaxf(m, fabsf(x[i]));
-    __shared__ float red[4];
-    block_max_to(out, m, red);
 }
 
 // ---------------------------------------------------------------- thin input (Cin <= 4 -> 160)
@@ -427,7 +407,8 @@ __global__ void __launch_bounds__(256, GW ? 2 : 1) conv3d_thin_out_f16x3_kernel(
     }
 }
 
-// v2 of the thin-output kernel: the whole packed weight image (5 chunks x 9
+#ifdef DLCS_DIAG_BUILD
+// v2 of the thin-output kernel (DLCS_THIN_OUT_V2=1): the whole packed weight image (5 chunks x 9
 // (kd, kh) x 2 planes x 4 k groups x the 12 used (kw, co) columns, 69 KB) is
 // copied into LDS once per persistent workgroup, next to the chunk halo (76.8 KB),
 // so the K loop has no weight traffic; the (tile, chunk) items a workgroup walks
@@ -435,7 +416,6 @@ __global__ void __launch_bounds__(256, GW ? 2 : 1) conv3d_thin_out_f16x3_kernel(
 // sets (the next tile's first chunk is in flight during the last chunk's MFMAs
 // and the epilogue).  Lanes of the unused columns 12..15 read column 11 (their
 // Q columns are never read).
-constexpr int kThinOutW2 = 5 * 9 * 2 * 4 * 12 * 8;    // f16 of the LDS weight image
 __global__ void __launch_bounds__(256, 1) conv3d_thin_out_f16x3_v2_kernel(ConvF32Args a, const f16* wimg,
                                                                           const unsigned* xmax, int ntiles) {
     __shared__ __attribute__((aligned(16))) f16 smem_to4[kHalo * 64 + kThinOutW2];
@@ -578,6 +558,7 @@ __global__ void __launch_bounds__(256, 1) conv3d_thin_out_f16x3_v2_kernel(ConvF3
         if (s + 1 < nitems) body(hrb, s + 1);
     }
 }
+#endif  // DLCS_DIAG_BUILD
 
 // ---------------------------------------------------------------- wgrad, 160 <-> thin
 // dW = Big^T . Thin_im2col with the tap shift on the thin side (u = v + off):
@@ -758,39 +739,32 @@ __global__ void __launch_bounds__(512, 1) conv3d_wgrad_thin_f16x3_kernel(ThinWgH
     }
 }
 
-// DLCS_THIN_OUT_V2=1: the thin-output kernel with LDS-resident weights (A/B timing; 510 vs 480 us)
-static bool thin_out_v1() {
-    static const bool v = [] { const char* e = dlcs_knob("DLCS_THIN_OUT_V2"); return !(e && e[0] == '1'); }();
-    return v;
-}
-
 static int conv_thin_f16x3_launch(const ConvF32Args& v, const f16* wimg, const unsigned* xmax, int cin, bool thin_in,
                                   hipStream_t st, f16* op = nullptr, const unsigned* opmax = nullptr,
                                   float* cpart = nullptr) {
-    const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
-    const int ntiles = (int)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
+    const int ntiles = (int)conv_tiles(v.B, v.D, v.H, v.W);
     const dim3 g(256);
     if (thin_in) {
-        int epi;
-        if (!v.res && !v.mask && !v.mplanes && !v.accumulate) epi = 0;
-        else if (!v.res && (v.mask || v.mplanes) && !v.accumulate) epi = kEpiMask;
-        else epi = kEpiGeneric;
+        const int epi = conv_epi_code(v.res, v.mask || v.mplanes, !v.accumulate, false);
         if ((op || cpart || v.mplanes) && epi != kEpiMask) return DLCS_ERR_UNSUPPORTED_SIZE;   // the masked form only
-        if (epi == 0)
-            hipLaunchKernelGGL(conv3d_thin_in_f16x3_kernel<0>, g, dim3(512), 0, st, v, wimg, xmax, cin, ntiles, op, opmax,
-                               cpart);
-        else if (epi == kEpiMask)
-            hipLaunchKernelGGL(conv3d_thin_in_f16x3_kernel<kEpiMask>, g, dim3(512), 0, st, v, wimg, xmax, cin, ntiles, op,
-                               opmax, cpart);
-        else
-            hipLaunchKernelGGL(conv3d_thin_in_f16x3_kernel<kEpiGeneric>, g, dim3(512), 0, st, v, wimg, xmax, cin, ntiles,
-                               op, opmax, cpart);
-    } else if (thin_out_v1()) {
-        static const bool gw = [] { const char* e = dlcs_knob("DLCS_THIN_OUT_GW"); return !(e && e[0] == '0'); }();
-        if (gw) hipLaunchKernelGGL(conv3d_thin_out_f16x3_kernel<true>, dim3(512), dim3(256), 0, st, v, wimg, xmax, ntiles);
-        else hipLaunchKernelGGL(conv3d_thin_out_f16x3_kernel<false>, g, dim3(256), 0, st, v, wimg, xmax, ntiles);
+        auto launch = [&](auto E) {
+            hipLaunchKernelGGL(conv3d_thin_in_f16x3_kernel<decltype(E)::value>, g, dim3(512), 0, st, v, wimg, xmax, cin,
+                               ntiles, op, opmax, cpart);
+        };
+        if (epi == 0) launch(std::integral_constant<int, 0>{});
+        else if (epi == kEpiMask) launch(std::integral_constant<int, kEpiMask>{});
+        else launch(std::integral_constant<int, kEpiGeneric>{});
     } else {
-        hipLaunchKernelGGL(conv3d_thin_out_f16x3_v2_kernel, g, dim3(256), 0, st, v, wimg, xmax, ntiles);
+#ifdef DLCS_DIAG_BUILD
+        // DLCS_THIN_OUT_V2=1: the thin-output kernel with LDS-resident weights (A/B timing; 510 vs
+        // 480 us); DLCS_THIN_OUT_GW=0: the chunk's weights from an LDS copy, one workgroup per CU
+        static const bool v2 = [] { const char* e = dlcs_knob("DLCS_THIN_OUT_V2"); return e && e[0] == '1'; }();
+        static const bool gw = [] { const char* e = dlcs_knob("DLCS_THIN_OUT_GW"); return !(e && e[0] == '0'); }();
+        if (v2) hipLaunchKernelGGL(conv3d_thin_out_f16x3_v2_kernel, g, dim3(256), 0, st, v, wimg, xmax, ntiles);
+        else if (!gw) hipLaunchKernelGGL(conv3d_thin_out_f16x3_kernel<false>, g, dim3(256), 0, st, v, wimg, xmax, ntiles);
+        else
+#endif
+        hipLaunchKernelGGL(conv3d_thin_out_f16x3_kernel<true>, dim3(512), dim3(256), 0, st, v, wimg, xmax, ntiles);
     }
     return dlcs_launch_status();
 }

@@ -1,5 +1,5 @@
 // ---------------------------------------------------------------- thin ends from pre-split planes (round 5)
-// Included by conv3d.hip after conv3d_thin_f16x3.inc.  The 160-channel operand of
+// Part of conv3d_f16x3.hip.  The 160-channel operand of
 // the final conv's forward (relu(h), s3d:391) and weight gradient, and of the SFE
 // conv's input and weight gradients (g_s, s3d:384), as dlcs_split2_f16 plane
 // pairs [rows][320] (one split per tensor, shared by the two kernels that read
@@ -25,6 +25,7 @@ constexpr int kTpHY = 10, kTpHX = 6, kTpHalo = 6 * kTpHY * kTpHX;   // 360 halo 
 constexpr int kTpBuf = kTpHalo * 64;                                // f16 per halo buffer (45 KB)
 constexpr int kTpPieces = kTpHalo * 8 / 64;                         // 45 DMA wave-instructions per item
 
+#ifdef DLCS_DIAG_BUILD                                  // the two-buffer form: DLCS_THIN_OUT_P2=1
 __global__ void __launch_bounds__(512, 1) conv3d_thin_out_p_kernel(ConvF32Args a, const f16* xp, const f16* wimg,
                                                                    long rows) {
     __shared__ __attribute__((aligned(16))) f16 smem_tp[2 * kTpBuf + kThinOutW2];
@@ -185,6 +186,7 @@ __global__ void __launch_bounds__(512, 1) conv3d_thin_out_p_kernel(ConvF32Args a
         __syncthreads();
     }
 }
+#endif  // DLCS_DIAG_BUILD
 
 // Three-buffer form (round 6): the kernel above holds ONE item in flight per CU (one
 // 46 KB halo DMA, then a wait): a latency-bound 1.7 TB/s.  Here the weights leave LDS
@@ -373,9 +375,12 @@ static int conv_thin_out_p_launch(const ConvF32Args& v, const f16* xp, const f16
         return DLCS_ERR_UNSUPPORTED_SIZE;
     // 8 XCDs x 32 workgroups (one per CU): one 4 x 8-tile block per XCD and round;
     // DLCS_THIN_OUT_P2=1 (DIAG build): the two-buffer kernel with LDS weights, for A/B timing
+#ifdef DLCS_DIAG_BUILD
     static const bool p2 = [] { const char* e = dlcs_knob("DLCS_THIN_OUT_P2"); return e && e[0] == '1'; }();
     if (p2) hipLaunchKernelGGL(conv3d_thin_out_p_kernel, dim3(256), dim3(512), 0, st, v, xp, wimg, rows);
-    else hipLaunchKernelGGL(conv3d_thin_out_p3_kernel, dim3(256), dim3(512), 0, st, v, xp, wimg, rows);
+    else
+#endif
+    hipLaunchKernelGGL(conv3d_thin_out_p3_kernel, dim3(256), dim3(512), 0, st, v, xp, wimg, rows);
     return dlcs_launch_status();
 }
 
@@ -474,8 +479,7 @@ __global__ void __launch_bounds__(512, 1) conv3d_wgrad_thin_p_kernel(ThinWgPArgs
             const bool ok = tok && (unsigned)(py * 4 + y + skh) < (unsigned)a.H && (unsigned)(px * 4 + x + skw) < (unsigned)a.W;
             const int hv = (t + 1 + skd) * 36 + (y + 1 + skh) * 6 + (x + 1 + skw);
             f32x4_t v = *reinterpret_cast<const f32x4_t*>(TR + hv * 4);
-            typedef _Float16 f16x4_tt __attribute__((ext_vector_type(4)));
-            f16x4_tt h, l;
+            f16x4_t h, l;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float u = (ok && e < a.thin_ch) ? v[e] * st : 0.0f;
@@ -485,8 +489,8 @@ __global__ void __launch_bounds__(512, 1) conv3d_wgrad_thin_p_kernel(ThinWgPArgs
             }
             const int un = t >> 1, row = (t & 1) * 16 + y * 4 + x;
             const int col = (jtap * 4) ^ (((row >> 3) & 1) << 4);
-            *reinterpret_cast<f16x4_tt*>(IM + (un * 2 + 0) * kTwIm + row * 128 + col) = h;
-            *reinterpret_cast<f16x4_tt*>(IM + (un * 2 + 1) * kTwIm + row * 128 + col) = l;
+            *reinterpret_cast<f16x4_t*>(IM + (un * 2 + 0) * kTwIm + row * 128 + col) = h;
+            *reinterpret_cast<f16x4_t*>(IM + (un * 2 + 1) * kTwIm + row * 128 + col) = l;
         }
     };
 

@@ -1,5 +1,5 @@
 // ---------------------------------------------------------------- bf16 Conv3d 160 -> 160, v6
-// Included by conv3d.hip after conv3d_f16x3.inc.  The bf16 160-channel forward /
+// Included by conv3d.hip.  The bf16 160-channel forward /
 // input gradient (s3d:336, :356; config 2's dtype) on the f16x3 kernel's
 // structure, with one bf16 product per tap instead of three plane products:
 //   * tile, waves, fragments and LDS images of conv3d_k3_v5_kernel: 256 voxels
@@ -25,13 +25,6 @@
 // Weights: dlcs_conv3d_pack_weights bf16 modes 0 / 1 (the v5 packing, cin_pad 160).
 constexpr int kV6Slot = 6 * 160 * 32;                   // bf16 per weight slot (6 taps x 160 co x 32 ci)
 constexpr int kV6Steps = 5;                             // steps per chunk: rows {0,1} {2,3} {4,5} {6,7} {8}
-
-struct ConvV6Args {
-    ConvV2Args v;
-    int tail_base;                                      // TAIL: workgroup w computes tile tail_base + w / 5, chunk w % 5
-    float* part;                                        // TAIL: raw partial tiles [5 ntail][256][160]
-    int exp;                                            // DIAG build: DLCS_V6_EXP / DLCS_V7_EXP bits
-};
 
 // tile vb (XCD-major virtual numbering over nblk tiles) -> (b, pt, tyy, txx)
 DLCS_DEV void v6_tile(int vb, int nblk, int nT, int nYt, int nXt, int& b, int& pt, int& tyy, int& txx) {
@@ -301,26 +294,17 @@ __global__ void __launch_bounds__(256) conv_v6_tail_reduce_kernel(ConvV6Args g, 
 // tail_ws: conv_tail_bytes(tiles) bytes for the tail split's partial tiles
 static int conv_v6_launch(const ConvV2Args& v, float* tail_ws, hipStream_t st) {
     if ((long)v.B * v.D * v.H * v.W * v.cin_ld >= (1L << 31)) return DLCS_ERR_UNSUPPORTED_SIZE;   // 32-bit halo offsets
-    const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
-    const unsigned nblk = (unsigned)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
+    const unsigned nblk = (unsigned)conv_tiles(v.B, v.D, v.H, v.W);
     const char* te = dlcs_test_hook("DLCS_V6_TAIL");                 // read per launch (tests toggle it)
     const bool tail_split = !(te && te[0] == '0');
     const unsigned ntail = tail_split ? conv_tail_tiles(nblk) : 0u, nmain = nblk - ntail;
     const bool split = ntail > 0;
-    ConvV6Args g{};
-    g.v = v;
+    ConvV6Args g{v};
 #ifdef DLCS_DIAG_BUILD
-    {
-        const char* e = dlcs_knob("DLCS_V6_EXP");      // read per launch: 128 = no scheduling fences
-        g.exp = e ? atoi(e) : 0;
-    }
+    if (const char* e = dlcs_knob("DLCS_V6_EXP")) g.exp = atoi(e);   // read per launch: 128 = no scheduling fences
 #endif
     if (split) g.part = tail_ws;
-    int epi;
-    if (!v.res && !v.mask && !v.accumulate && !v.out_f32) epi = 0;
-    else if (v.res && !v.res_f32 && !v.mask && !v.accumulate && !v.out_f32) epi = kEpiRes;
-    else if (!v.res && v.mask && !v.accumulate && !v.out_f32) epi = kEpiMask;
-    else epi = kEpiGeneric;
+    const int epi = conv_epi_code(v.res, v.mask, !v.accumulate && !v.out_f32, !v.res_f32);   // fused residual: bf16
     const dim3 gm(split ? nmain : nblk);
     if (epi == 0) hipLaunchKernelGGL((conv3d_k3_v6_kernel<0, false>), gm, dim3(512), 0, st, g);
     else if (epi == kEpiRes) hipLaunchKernelGGL((conv3d_k3_v6_kernel<kEpiRes, false>), gm, dim3(512), 0, st, g);

@@ -1,5 +1,5 @@
 // ---------------------------------------------------------------- bf16 Conv3d 160 -> 160, v7
-// Included by conv3d.hip after conv3d_v6.inc.  The bf16 160-channel forward / input
+// Included by conv3d.hip.  The bf16 160-channel forward / input
 // gradient (s3d:336, :356; config 2's dtype) with TWO workgroups per CU.  The v6
 // kernel (one 157.5 KB workgroup of 8 waves per CU) pays every barrier, end-of-step
 // drain and epilogue with the whole CU idle; here the unit of work is half of v6's
@@ -320,27 +320,18 @@ __global__ void __launch_bounds__(256) conv_v7_tail_reduce_kernel(ConvV6Args g, 
 // tail_ws: conv_tail_bytes(tiles) bytes, as v6 (twice the tail units of half the channels)
 static int conv_v7_launch(const ConvV2Args& v, float* tail_ws, hipStream_t st) {
     if ((long)v.B * v.D * v.H * v.W * v.cin_ld >= (1L << 31)) return DLCS_ERR_UNSUPPORTED_SIZE;   // 32-bit halo offsets
-    const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
-    const unsigned nunit = 2u * (unsigned)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
+    const unsigned nunit = 2u * (unsigned)conv_tiles(v.B, v.D, v.H, v.W);
     const char* te = dlcs_test_hook("DLCS_V7_TAIL");                 // read per launch (tests toggle it)
     const bool tail_split = !(te && te[0] == '0');
     // one round = 512 workgroups (two per CU): the units of v6's tail tiles
     const unsigned ntail = tail_split ? 2u * conv_tail_tiles(nunit / 2) : 0u, nmain = nunit - ntail;
     const bool split = ntail > 0;
-    ConvV6Args g{};
-    g.v = v;
+    ConvV6Args g{v};
 #ifdef DLCS_DIAG_BUILD
-    {
-        const char* e = dlcs_knob("DLCS_V7_EXP");      // read per launch (timing experiments)
-        g.exp = e ? atoi(e) : 0;
-    }
+    if (const char* e = dlcs_knob("DLCS_V7_EXP")) g.exp = atoi(e);   // read per launch (timing experiments)
 #endif
     if (split) g.part = tail_ws;                        // ntail units x 5 x 256 x 80 floats
-    int epi;
-    if (!v.res && !v.mask && !v.accumulate && !v.out_f32) epi = 0;
-    else if (v.res && !v.res_f32 && !v.mask && !v.accumulate && !v.out_f32) epi = kEpiRes;
-    else if (!v.res && v.mask && !v.accumulate && !v.out_f32) epi = kEpiMask;
-    else epi = kEpiGeneric;
+    const int epi = conv_epi_code(v.res, v.mask, !v.accumulate && !v.out_f32, !v.res_f32);   // fused residual: bf16
     const dim3 gm(split ? nmain : nunit);
     if (epi == 0) hipLaunchKernelGGL((conv3d_k3_v7_kernel<0, false>), gm, dim3(256), 0, st, g);
     else if (epi == kEpiRes) hipLaunchKernelGGL((conv3d_k3_v7_kernel<kEpiRes, false>), gm, dim3(256), 0, st, g);

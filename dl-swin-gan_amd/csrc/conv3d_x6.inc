@@ -281,13 +281,8 @@ __global__ void pack_weights_x6_kernel(const float* w, bf16* wa, bf16* wb, int m
 }
 
 static int conv_x6_launch(const ConvX6Args& v, hipStream_t st) {
-    const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
-    const unsigned nblk = (unsigned)((long)v.B * nT * ((nY + 1) / 2) * ((nX + 1) / 2));
-    int epi;
-    if (!v.res && !v.mask && !v.accumulate) epi = 0;
-    else if (v.res && !v.mask && !v.accumulate) epi = kEpiRes;
-    else if (!v.res && v.mask && !v.accumulate) epi = kEpiMask;
-    else epi = kEpiGeneric;
+    const unsigned nblk = (unsigned)conv_tiles(v.B, v.D, v.H, v.W);
+    const int epi = conv_epi_code(v.res, v.mask, !v.accumulate, true);
     if (epi == 0) hipLaunchKernelGGL(conv3d_k3_x6_kernel<0>, dim3(nblk), dim3(512), 0, st, v);
     else if (epi == kEpiRes) hipLaunchKernelGGL(conv3d_k3_x6_kernel<kEpiRes>, dim3(nblk), dim3(512), 0, st, v);
     else if (epi == kEpiMask) hipLaunchKernelGGL(conv3d_k3_x6_kernel<kEpiMask>, dim3(nblk), dim3(512), 0, st, v);

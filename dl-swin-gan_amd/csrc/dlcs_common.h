@@ -147,6 +147,14 @@ static inline int dlcs_launch_status() {
 
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
+// Caller workspaces: each size is one host function that both the dlcs_*_workspace_bytes
+// query and the launch call; a size a test hook or DIAG knob can change is the largest.
+static inline size_t ws_align(size_t n) { return (n + 255) & ~(size_t)255; }   // sub-buffers at 256-B offsets
+static inline bool ws_ok(const void* ws, size_t have, size_t need) { return need == 0 || (ws && have >= need); }
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }   // 16-B accesses (torch allocations are aligned)
+// trailer of a split2 plane buffer of `rows` rows of 640 B: the bits of max |x| (or its bound) first
+static inline unsigned* planes_trailer(const void* planes, long rows) { return (unsigned*)((const char*)planes + rows * 640); }
+
 // Diagnostic switches (superseded kernels kept for A/B measurement, tuning
 // overrides, stamps) exist only in the DIAG build (`make DIAG=1` ->
 // libdlcs_hip_diag.so, which also holds the superseded bf16 3-plane conv and NT

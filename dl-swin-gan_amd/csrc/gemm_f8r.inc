@@ -1,5 +1,5 @@
 // ---------------------------------------------------------------- fp8 (OCP e4m3) token GEMM, row-scaled (f8r)
-// Included by conv3d.hip after gemm_h3r.inc.  The fp8 MFMA path of the diffusion
+// Included by gemm_f16x3.hip.  The fp8 MFMA path of the diffusion
 // denoisers (BASELINE config 5, DiT / Latte token Linears, inference):
 //   C[row(m), n] = alpha act(sum_k A[m, k] B[n, k] / (s_a[m] s_b[n]) + bias[n]) + res[row(m), n]
 // with A and B quantised to e4m3 by dlcs_f8r_quant: one power-of-two scale per

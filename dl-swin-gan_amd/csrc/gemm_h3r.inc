@@ -1,5 +1,5 @@
 // ---------------------------------------------------------------- fp32 token Linears on fp16 matrix cores, row-scaled split (h3r)
-// Included by conv3d.hip after conv3d_f16x3.inc (mfma16h, f16x3_scale, glds16).
+// Included by gemm_f16x3.hip (mfma16h, f16x3_scale: f16x3_common.h; glds16: lds_dma.h).
 //
 // C[row(m), n] (+)= alpha act(sum_k A[m, k] B[n, k] + bias[n]) + res[row(m), n]
 // for the fp32 token Linears: the Swin block's (vst:146, :168, :33-37; K in
@@ -121,7 +121,6 @@ __global__ void __launch_bounds__(512, 2) gemm_h3r_kernel(GemmH3rArgs g) {
     const int aoh = ar * 64 + (((aj >> 1) ^ asw) << 3) + (aj & 1) * 4;
     const int aol = ar * 64 + (((4 + (aj >> 1)) ^ asw) << 3) + (aj & 1) * 4;
     auto split_a = [&](const f32x4_t& v, int slot) {
-        typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
         f16x4_t h, l;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -342,7 +341,6 @@ __global__ void __launch_bounds__(256) h3r_pack_kernel(H3rPackBatch bt) {
     }
     __syncthreads();
     const long dld = (long)jb.K * 2;
-    typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
     for (int c = c0 + wave; c < c1; c += 4) {
         if (jb.trans) {
             const float sc = scl[lane];
