@@ -126,6 +126,16 @@ SIGNATURES = {
     "dlcs_scale_rows": [_P, _P, _P, _P, _P, _I64, _I64, _P],
     "dlcs_gated_linear_grad": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P],
     "dlcs_rows_add": [_P, _P, _P, _I64, _I64, _P],
+    # squeeze-excitation gate of the SE-ResNet (se.hip)
+    "dlcs_se_pool_workspace_bytes": [_I64, _I64, _I64],
+    "dlcs_se_pool": [_P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
+    "dlcs_se_gate": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P],
+    "dlcs_se_scale_res_relu": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "dlcs_se_bwd_reduce_workspace_bytes": [_I64, _I64, _I64],
+    "dlcs_se_bwd_reduce": [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
+    "dlcs_se_gate_bwd_workspace_bytes": [_I64, _I64, _I64],
+    "dlcs_se_gate_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "dlcs_se_bwd_apply": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
 }
 # DIAG build only (libdlcs_hip_diag.so: the superseded bf16 3-plane conv and NT GEMM);
 # bound when the loaded library has them

@@ -640,3 +640,67 @@ def relu_grad(g, a):
     assert g.numel() == a.numel()
     call("dlcs_relu_grad", code(g), p(g), code(a), p(a), g.numel(), S())
     return g
+
+
+# ---------------------------------------------------------------------------- squeeze-excitation
+# fp32 rows [B N, ld] (batch item b = rows [b N, (b + 1) N)) with C channels; dlcs.h "se.hip"
+def se_pool(o, B, N, C, mean=None):
+    """mean [B, C] = the per-(batch item, channel) average of o over its N rows (dlcs_se_pool)."""
+    if mean is None:
+        mean = empty((B, C), torch.float32, o.device)
+    ws, nb = _ws("dlcs_se_pool", o.device, B, N, C)
+    call("dlcs_se_pool", p(o), B, N, C, o.shape[-1], p(mean), p(ws), nb, S())
+    return mean
+
+
+def se_gate(mean, w1, b1, w2, b2, hidden=None, gate=None):
+    """hidden [B, R] = relu(W1 mean + b1), gate [B, C] = sigmoid(W2 hidden + b2) (dlcs_se_gate)."""
+    B, C = mean.shape
+    R = w1.shape[0]
+    if hidden is None:
+        hidden = empty((B, R), torch.float32, mean.device)
+    if gate is None:
+        gate = empty((B, C), torch.float32, mean.device)
+    call("dlcs_se_gate", p(mean), p(w1), p(b1), p(w2), p(b2), B, C, R, p(hidden), p(gate), S())
+    return hidden, gate
+
+
+def se_scale_res_relu(o, gate, res, B, N, C, out=None):
+    """out = relu(o gate[b, c] + res) (dlcs_se_scale_res_relu); out may be res, not o."""
+    if out is None:
+        out = empty(o.shape, torch.float32, o.device)
+    assert o.shape[-1] == res.shape[-1] == out.shape[-1]
+    call("dlcs_se_scale_res_relu", p(o), p(gate), p(res), p(out), B, N, C, o.shape[-1], S())
+    return out
+
+
+def se_bwd_reduce(g, r_next, o, B, N, C, dgate=None):
+    """dgate [B, C] = sum over a batch item's rows of g (r_next > 0) o (dlcs_se_bwd_reduce)."""
+    if dgate is None:
+        dgate = empty((B, C), torch.float32, g.device)
+    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1]
+    ws, nb = _ws("dlcs_se_bwd_reduce", g.device, B, N, C)
+    call("dlcs_se_bwd_reduce", p(g), p(r_next), p(o), B, N, C, g.shape[-1], p(dgate), p(ws), nb, S())
+    return dgate
+
+
+def se_gate_bwd(dgate, gate, hidden, mean, w1, w2, inv_n, dw1, db1, dw2, db2, dmean=None):
+    """Backward of se_gate: dw1 / db1 / dw2 / db2 += the FC gradients, returns
+    dmean [B, C] = (dh W1) inv_n (dlcs_se_gate_bwd)."""
+    B, C = gate.shape
+    R = hidden.shape[1]
+    if dmean is None:
+        dmean = empty((B, C), torch.float32, gate.device)
+    ws, nb = _ws("dlcs_se_gate_bwd", gate.device, B, C, R)
+    call("dlcs_se_gate_bwd", p(dgate), p(gate), p(hidden), p(mean), p(w1), p(w2), B, C, R, float(inv_n),
+         p(dw1), p(db1), p(dw2), p(db2), p(dmean), p(ws), nb, S())
+    return dmean
+
+
+def se_bwd_apply(g, r_next, gate, dmean, B, N, C, dout=None):
+    """g *= (r_next > 0) in place; returns dout = g gate[b, c] + dmean[b, c] (dlcs_se_bwd_apply)."""
+    if dout is None:
+        dout = empty(g.shape, torch.float32, g.device)
+    assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1]
+    call("dlcs_se_bwd_apply", p(g), p(r_next), p(gate), p(dmean), p(dout), B, N, C, g.shape[-1], S())
+    return dout

@@ -631,6 +631,49 @@ int dlcs_gated_linear_grad(const float* W, const float* b, const float* G, const
                            float* dW, float* db, float* dgate, int64_t N, int64_t K, dlcs_stream_t stream);
 int dlcs_rows_add(float* dst, const int32_t* idx, const float* src, int64_t nrows, int64_t C, dlcs_stream_t stream);
 
+/* ---- Squeeze-excitation gate of the SE-ResNet (se.hip) -----------------------------
+ * se3d = dl_cs/models/se3d.py: SeBlock :302-348 (GlobalAvgPool :80-97 -> FC -> ReLU ->
+ * FC -> sigmoid) and the gated residual of SeResBlock :435-438.  fp32, on the
+ * patch-blocked rows [B N, ld] of a conv output with C channels; batch item b is the
+ * rows [b N, (b + 1) N), N = Tp Y X voxels (time pad included).  W1 [R, C], b1 [R],
+ * W2 [C, R], b2 [C] are the two nn.Linear of the block (R = the config's RR, the hidden
+ * width).  1 <= C <= 1024, 1 <= R <= 256, B <= 65535 for the row passes: beyond,
+ * DLCS_ERR_UNSUPPORTED_SIZE and nothing is written.  Rows are read and written 16 B at a
+ * time when C % 4 == 0, ld % 4 == 0 and the row pointers are 16-B aligned, else one
+ * float at a time; columns [C, ld) are never read or written.
+ *
+ *   pool:           mean[b, c] = (1 / N) sum_rows o
+ *   gate:           hidden[b, :] = relu(W1 mean[b] + b1) (kept for the backward),
+ *                   gate[b, :] = sigmoid(W2 hidden[b] + b2), one launch
+ *   scale_res_relu: out = relu(o gate[b, c] + res); out may alias res, not o
+ *   bwd_reduce:     dgate[b, c] = sum_rows g [r_next > 0] o (relu_grad's rule: only
+ *                   r_next > 0 keeps a row's term; NaN, +-0 and negatives drop it)
+ *   gate_bwd:       dz2 = dgate gate (1 - gate); dW2 += dz2^T hidden; db2 += sum_b dz2;
+ *                   dh = (dz2 W2) [hidden > 0]; dW1 += dh^T mean; db1 += sum_b dh;
+ *                   dmean = (dh W1) inv_n.  Batch sums in ascending b.
+ *   bwd_apply:      g <- g [r_next > 0] in place (bitwise dlcs_relu_grad),
+ *                   dout = g gate[b, c] + dmean[b, c]; dout may not alias g
+ *
+ * The reductions store one partial row per workgroup in `workspace` and a second
+ * launch sums them in a fixed order: no float atomics, the same input gives the same
+ * bits.  Too small a workspace: DLCS_ERR_WORKSPACE before anything is launched.       */
+size_t dlcs_se_pool_workspace_bytes(int64_t B, int64_t N, int64_t C);
+int dlcs_se_pool(const float* o, int64_t B, int64_t N, int64_t C, int64_t ld, float* mean, void* workspace,
+                 size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_se_gate(const float* mean, const float* W1, const float* b1, const float* W2, const float* b2, int64_t B,
+                 int64_t C, int64_t R, float* hidden, float* gate, dlcs_stream_t stream);
+int dlcs_se_scale_res_relu(const float* o, const float* gate, const float* res, float* out, int64_t B, int64_t N,
+                           int64_t C, int64_t ld, dlcs_stream_t stream);
+size_t dlcs_se_bwd_reduce_workspace_bytes(int64_t B, int64_t N, int64_t C);
+int dlcs_se_bwd_reduce(const float* g, const float* r_next, const float* o, int64_t B, int64_t N, int64_t C, int64_t ld,
+                       float* dgate, void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
+size_t dlcs_se_gate_bwd_workspace_bytes(int64_t B, int64_t C, int64_t R);
+int dlcs_se_gate_bwd(const float* dgate, const float* gate, const float* hidden, const float* mean, const float* W1,
+                     const float* W2, int64_t B, int64_t C, int64_t R, float inv_n, float* dW1, float* db1, float* dW2,
+                     float* db2, float* dmean, void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_se_bwd_apply(float* g, const float* r_next, const float* gate, const float* dmean, float* dout, int64_t B,
+                      int64_t N, int64_t C, int64_t ld, dlcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

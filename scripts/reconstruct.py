@@ -70,11 +70,12 @@ class CflDataset:
 
 def build_model(config):
     """reconstruct_h5.py:398-406 -- MODEL_TYPE 'SWIN' (LitUnrolledSWIN, :97-122) or
-    'RES' (LitUnrolledResNet: dl_cs.models.unrolled, the ResNet of configs/example.yaml)."""
-    from dl_cs.models import unrolled, unrolledswin
-    mods = {'SWIN': unrolledswin, 'RES': unrolled}
+    'RES' (LitUnrolledResNet: dl_cs.models.unrolled, the ResNet of configs/example.yaml) or
+    'SE' (LitUnrolledSE: dl_cs.models.unrolledSE, configs/config_se.yaml)."""
+    from dl_cs.models import unrolled, unrolledSE, unrolledswin
+    mods = {'SWIN': unrolledswin, 'RES': unrolled, 'SE': unrolledSE}
     if config.MODEL.MODEL_TYPE not in mods:
-        raise NotImplementedError(f"MODEL_TYPE {config.MODEL.MODEL_TYPE}: SWIN and RES are built for MI355X")
+        raise NotImplementedError(f"MODEL_TYPE {config.MODEL.MODEL_TYPE}: SWIN, RES and SE are built for MI355X")
     mod = mods[config.MODEL.MODEL_TYPE]
     if config.MODEL.META_ARCHITECTURE == 'dlespirit':
         return mod.ProximalGradientDescent(config)

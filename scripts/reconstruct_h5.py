@@ -78,11 +78,11 @@ class Hdf5Dataset:
 
 
 def build_model(config, model_type):
-    """rh5:398-406 -- the Lit* wrapper by --model: SWIN (:98-122) or RES (:46-70)."""
-    from dl_cs.models import unrolled, unrolledswin
-    mods = {'SWIN': unrolledswin, 'RES': unrolled}
+    """rh5:398-406 -- the Lit* wrapper by --model: SWIN (:98-122), RES (:46-70) or SE (unrolledSE)."""
+    from dl_cs.models import unrolled, unrolledSE, unrolledswin
+    mods = {'SWIN': unrolledswin, 'RES': unrolled, 'SE': unrolledSE}
     if model_type not in mods:
-        raise NotImplementedError(f"--model {model_type}: SWIN and RES are built for MI355X")
+        raise NotImplementedError(f"--model {model_type}: SWIN, RES and SE are built for MI355X")
     if config.MODEL.META_ARCHITECTURE == 'dlespirit':
         return mods[model_type].ProximalGradientDescent(config)
     if config.MODEL.META_ARCHITECTURE == 'modl':
@@ -143,7 +143,7 @@ def main(args):
 def create_arg_parser():
     parser = argparse.ArgumentParser(description="Inference script for unrolled MRI recon (H5 input).")
     parser.add_argument('--file', type=str, required=True, help='Name of the H5 file with kspace, mask, and map')
-    parser.add_argument('--model', type=str, required=True, help='SWIN (Swin-unrolled) or RES (unrolled ResNet)')
+    parser.add_argument('--model', type=str, required=True, help='SWIN (Swin-unrolled), RES (unrolled ResNet) or SE (unrolled SE-ResNet)')
     parser.add_argument('--acceleration', type=int, default=1, help='Undersampling Accelration Factor')
     parser.add_argument('--out-directory', type=str, required=True, help='Output Directory')
     parser.add_argument('--ckpt', type=str, required=True, help='Model checkpoint file')

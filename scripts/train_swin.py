@@ -52,9 +52,13 @@ logger = logging.getLogger("train_swin")
 def build_model(config):
     """train_swin.py:46-51 (MODEL_TYPE 'SWIN'); MODEL_TYPE 'RES' builds the reference's
     scripts/train.py model -- dl_cs.models.unrolled with the 3-D ResNet of
-    configs/example.yaml (BASELINE config 1)."""
-    from dl_cs.models import unrolled, unrolledswin
-    mod = unrolledswin if config.MODEL.MODEL_TYPE.upper() == 'SWIN' else unrolled
+    configs/example.yaml (BASELINE config 1); MODEL_TYPE 'SE' the reference's
+    scripts/train_se.py model -- dl_cs.models.unrolledSE (configs/config_se.yaml)."""
+    from dl_cs.models import unrolled, unrolledSE, unrolledswin
+    mods = {'SWIN': unrolledswin, 'RES': unrolled, 'SE': unrolledSE}
+    if config.MODEL.MODEL_TYPE.upper() not in mods:
+        raise NotImplementedError(f"MODEL_TYPE {config.MODEL.MODEL_TYPE}: SWIN, RES and SE are built for MI355X")
+    mod = mods[config.MODEL.MODEL_TYPE.upper()]
     arch = config.MODEL.META_ARCHITECTURE
     if arch == 'dlespirit':
         return mod.ProximalGradientDescent(config)
