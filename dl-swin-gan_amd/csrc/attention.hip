@@ -844,7 +844,7 @@ __global__ void __launch_bounds__(kBwdWaves * 64) attn_bwd_kv_kernel(AttnArgs a)
             for (int r = 0; r < 16; ++r) {
                 const int q = qb * 32 + acc_row(r, lane);
                 const float okf = (kvalid && q < N) ? 1.0f : 0.0f;
-                const float v = s[r] + bv[r] + mask_term<MM>(a, w, q, key, qi[r], kinfo);
+                const float v = s[r] + bv[r] + mask_term<MM>(a, w, min(q, N - 1), min(key, N - 1), qi[r], kinfo);
                 p[r] = okf * __expf(v - lv[r]);
                 ds[r] = p[r] * (dp[r] - dv_[r]);
             }
@@ -971,7 +971,7 @@ __global__ void __launch_bounds__(kBwdWaves * 64) attn_bwd_q_kernel(AttnArgs a) 
         for (int r = 0; r < 16; ++r) {
             const int key = kb * 32 + acc_row(r, lane);
             const float okf = (qvalid && key < N) ? 1.0f : 0.0f;
-            const float v = s[r] + bv[r] + mask_term<MM>(a, w, q, key, qinfo, ki[r]);
+            const float v = s[r] + bv[r] + mask_term<MM>(a, w, min(q, N - 1), min(key, N - 1), qinfo, ki[r]);
             ds[r] = okf * __expf(v - lse) * (dp[r] - D);
         }
 #pragma unroll
@@ -1136,14 +1136,16 @@ int dlcs_window_attn_bwd(int dtype, const void* qkv, const void* out, const void
     if (dtype == DLCS_F32 && head_dim == 20 && !attn_f32_generic())
     {
         if (attn_bwd_h3()) { const int rc = attn_bwd_h3_launch(a, st); if (rc != DLCS_ERR_UNSUPPORTED_SIZE) return rc; }
+        // a refused call writes nothing: the size check comes before the memset
+        if (bwd_kv_f32_smem<20>(a) > 160 * 1024 || bwd_q_f32_smem<20>(a) > 160 * 1024) return DLCS_ERR_UNSUPPORTED_SIZE;
         if (hipMemsetAsync(dqkv, 0, dq_bytes, st) != hipSuccess) return dlcs_launch_status();
         return attn_bwd_f32_launch<20>(a, st);
     }
     if (dtype == DLCS_F32) {
-        if (hipMemsetAsync(dqkv, 0, dq_bytes, st) != hipSuccess) return dlcs_launch_status();
         constexpr int NK = AttnCfg<float>::BWD_WAVES * 32;
         size_t sm = bwd_smem<float>(a);
         if (sm > 160 * 1024) return DLCS_ERR_UNSUPPORTED_SIZE;
+        if (hipMemsetAsync(dqkv, 0, dq_bytes, st) != hipSuccess) return dlcs_launch_status();
         dim3 grid((unsigned)(nwin * heads), cdiv(N, NK));
         (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
         hipLaunchKernelGGL(attn_bwd_kernel<float>, grid, dim3(AttnCfg<float>::BWD_WAVES * 64), sm, st, a);

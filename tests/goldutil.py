@@ -180,3 +180,66 @@ def assert_masked_f64(hip, lf, sd, trainable, masks, label, min_tol=1e-5, factor
     print(f"{label}: {n} HIP ReLU decisions differ from the float64 oracle's, largest |pre-act|/rms {rel:.3g}")
     assert rel < 1e-4, (label, n, rel)
     assert_f64_floor(hip, o32, o64, label + " (HIP masks)", min_tol, factor)
+
+
+def attn_reference(qkv, table, labels, mask, nwin, N, heads, hd, window, scale, dout, round_q=True,
+                   with_lse=False):
+    """float64 window attention fwd + bwd on the (already rounded) operands:
+    vst:139-170 with the relative-position bias of vst:111-129 and the -100 shift
+    mask of vst:342-355 (from region labels) or an explicit additive mask.
+    Returns (out, dqkv, dtable), with_lse: also the log-sum-exp [nwin, heads, N]."""
+    import itertools
+    import torch
+    wd, wh, ww = window
+    coords = torch.tensor(list(itertools.product(range(wd), range(wh), range(ww))))[:N]
+    rel = coords[:, None, :] - coords[None, :, :]
+    idx = (rel[..., 0] + wd - 1) * (2 * wh - 1) * (2 * ww - 1) + (rel[..., 1] + wh - 1) * (2 * ww - 1) + rel[..., 2] + ww - 1
+    C = heads * hd
+    x = qkv.double().view(nwin, N, 3, heads, hd).permute(2, 0, 3, 1, 4)        # [3, nw, h, N, hd]
+    q = x[0] * scale
+    if round_q:
+        q = q.to(torch.bfloat16).double()                                       # the bf16 kernels round scale*q
+    q = q.requires_grad_()
+    k = x[1].clone().requires_grad_()
+    v = x[2].clone().requires_grad_()
+    tb = table.double().clone().requires_grad_()
+    s = q @ k.transpose(-1, -2) + tb[idx.reshape(-1)].reshape(N, N, heads).permute(2, 0, 1)[None]
+    if labels is not None:
+        lab = labels.view(nwin, N)
+        s = s + torch.where(lab[:, None, :, None] != lab[:, None, None, :], -100.0, 0.0).double()
+    if mask is not None:
+        s = s + mask.double()[torch.arange(nwin) % mask.shape[0]][:, None]
+    o = torch.softmax(s, -1) @ v                                                # [nw, h, N, hd]
+    o.backward(dout.double().view(nwin, N, heads, hd).permute(0, 2, 1, 3))
+    out = o.permute(0, 2, 1, 3).reshape(nwin * N, C)
+    dq = (q.grad * scale).permute(0, 2, 1, 3).reshape(nwin * N, C)
+    dk = k.grad.permute(0, 2, 1, 3).reshape(nwin * N, C)
+    dv = v.grad.permute(0, 2, 1, 3).reshape(nwin * N, C)
+    res = (out.detach(), torch.cat([dq, dk, dv], 1).detach(), tb.grad.detach())
+    return res + (torch.logsumexp(s, -1).detach(),) if with_lse else res
+
+
+def attn_fwd_dtype(qkv, table, labels, mask, nwin, N, heads, hd, window, scale, dt, dout=None):
+    """Window attention evaluated in dtype dt: out [rows, C], lse [nwin, heads, N] and,
+    with dout, (dqkv [rows, 3C], dtable)."""
+    import itertools
+    import torch
+    wd, wh, ww = window
+    coords = torch.tensor(list(itertools.product(range(wd), range(wh), range(ww))))[:N]
+    rel = coords[:, None, :] - coords[None, :, :]
+    idx = (rel[..., 0] + wd - 1) * (2 * wh - 1) * (2 * ww - 1) + (rel[..., 1] + wh - 1) * (2 * ww - 1) + rel[..., 2] + ww - 1
+    xq = qkv.to(dt).clone().requires_grad_()
+    tb = table.to(dt).clone().requires_grad_()
+    x = xq.view(nwin, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
+    s = (x[0] * scale) @ x[1].transpose(-1, -2) + tb[idx.reshape(-1)].reshape(N, N, heads).permute(2, 0, 1)[None]
+    if labels is not None:
+        lab = labels.view(nwin, N)
+        s = s + torch.where(lab[:, None, :, None] != lab[:, None, None, :], -100.0, 0.0).to(dt)
+    if mask is not None:
+        s = s + mask.to(dt)[torch.arange(nwin) % mask.shape[0]][:, None]
+    o = (torch.softmax(s, -1) @ x[2]).permute(0, 2, 1, 3).reshape(nwin * N, heads * hd)
+    lse = torch.logsumexp(s, -1)
+    if dout is None:
+        return o.detach(), lse.detach()
+    o.backward(dout.to(dt))
+    return o.detach(), lse.detach(), xq.grad, tb.grad

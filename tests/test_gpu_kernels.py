@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from goldutil import attn_fwd_dtype as _attn_fwd_dtype
+from goldutil import attn_reference as _attn_reference
 from goldutil import nrmse
 
 pytestmark = pytest.mark.gpu
@@ -1037,39 +1039,6 @@ def test_layernorm_gather(dtype):
     assert nrmse(b_.grad.numpy(), db.cpu().double().numpy()) < 1e-6
 
 
-def _attn_reference(qkv, table, labels, mask, nwin, N, heads, hd, window, scale, dout, round_q=True):
-    """float64 window attention fwd + bwd on the (already rounded) operands:
-    vst:139-170 with the relative-position bias of vst:111-129 and the -100 shift
-    mask of vst:342-355 (from region labels) or an explicit additive mask."""
-    import itertools
-    wd, wh, ww = window
-    coords = torch.tensor(list(itertools.product(range(wd), range(wh), range(ww))))[:N]
-    rel = coords[:, None, :] - coords[None, :, :]
-    idx = (rel[..., 0] + wd - 1) * (2 * wh - 1) * (2 * ww - 1) + (rel[..., 1] + wh - 1) * (2 * ww - 1) + rel[..., 2] + ww - 1
-    C = heads * hd
-    x = qkv.double().view(nwin, N, 3, heads, hd).permute(2, 0, 3, 1, 4)        # [3, nw, h, N, hd]
-    q = x[0] * scale
-    if round_q:
-        q = q.to(torch.bfloat16).double()                                       # the bf16 kernels round scale*q
-    q = q.requires_grad_()
-    k = x[1].clone().requires_grad_()
-    v = x[2].clone().requires_grad_()
-    tb = table.double().clone().requires_grad_()
-    s = q @ k.transpose(-1, -2) + tb[idx.reshape(-1)].reshape(N, N, heads).permute(2, 0, 1)[None]
-    if labels is not None:
-        lab = labels.view(nwin, N)
-        s = s + torch.where(lab[:, None, :, None] != lab[:, None, None, :], -100.0, 0.0).double()
-    if mask is not None:
-        s = s + mask.double()[torch.arange(nwin) % mask.shape[0]][:, None]
-    o = torch.softmax(s, -1) @ v                                                # [nw, h, N, hd]
-    o.backward(dout.double().view(nwin, N, heads, hd).permute(0, 2, 1, 3))
-    out = o.permute(0, 2, 1, 3).reshape(nwin * N, C)
-    dq = (q.grad * scale).permute(0, 2, 1, 3).reshape(nwin * N, C)
-    dk = k.grad.permute(0, 2, 1, 3).reshape(nwin * N, C)
-    dv = v.grad.permute(0, 2, 1, 3).reshape(nwin * N, C)
-    return out.detach(), torch.cat([dq, dk, dv], 1).detach(), tb.grad.detach()
-
-
 @pytest.mark.parametrize("case", ["labels", "mask", "plain"])
 def test_window_attention_bf16_kernels(case):
     """bf16 fused window attention forward and the split backward (dK/dV/table
@@ -1125,31 +1094,6 @@ def test_window_attention_f32_kernels(case, N):
     for name, sl in (("dq", slice(0, C)), ("dk", slice(C, 2 * C)), ("dv", slice(2 * C, 3 * C))):
         assert nrmse(ref_dqkv[:, sl].numpy(), got[:, sl].numpy()) < 1e-5, name
     assert nrmse(ref_dt.numpy(), dt.double().cpu().numpy()) < 1e-5
-
-
-def _attn_fwd_dtype(qkv, table, labels, mask, nwin, N, heads, hd, window, scale, dt, dout=None):
-    """Window attention evaluated in dtype dt: out [rows, C], lse [nwin, heads, N] and,
-    with dout, (dqkv [rows, 3C], dtable)."""
-    import itertools
-    wd, wh, ww = window
-    coords = torch.tensor(list(itertools.product(range(wd), range(wh), range(ww))))[:N]
-    rel = coords[:, None, :] - coords[None, :, :]
-    idx = (rel[..., 0] + wd - 1) * (2 * wh - 1) * (2 * ww - 1) + (rel[..., 1] + wh - 1) * (2 * ww - 1) + rel[..., 2] + ww - 1
-    xq = qkv.to(dt).clone().requires_grad_()
-    tb = table.to(dt).clone().requires_grad_()
-    x = xq.view(nwin, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
-    s = (x[0] * scale) @ x[1].transpose(-1, -2) + tb[idx.reshape(-1)].reshape(N, N, heads).permute(2, 0, 1)[None]
-    if labels is not None:
-        lab = labels.view(nwin, N)
-        s = s + torch.where(lab[:, None, :, None] != lab[:, None, None, :], -100.0, 0.0).to(dt)
-    if mask is not None:
-        s = s + mask.to(dt)[torch.arange(nwin) % mask.shape[0]][:, None]
-    o = (torch.softmax(s, -1) @ x[2]).permute(0, 2, 1, 3).reshape(nwin * N, heads * hd)
-    lse = torch.logsumexp(s, -1)
-    if dout is None:
-        return o.detach(), lse.detach()
-    o.backward(dout.to(dt))
-    return o.detach(), lse.detach(), xq.grad, tb.grad
 
 
 @pytest.mark.parametrize("case,N,tail", [("labels", 448, False), ("plain", 96, False), ("mask", 100, False),
