@@ -108,7 +108,7 @@ def assert_f64_floor(hip, o32, o64, label, min_tol=1e-5, factor=4.0):
 # survives the network's column sums (bias and norm gradients over 3e5 rows) where
 # element errors average out: rounds 3-4 needed 5e-5 / 16x, then 2e-5 / 8x, here.
 # The input-gradient convs now alternate the sign of their per-step tiles (the
-# bias cancels; tools/dgrad_diag.py: column-sum error 2.1e-5 -> 5e-7), and every
+# bias cancels; profiles/r04s_grad_accuracy.txt: column-sum error 2.1e-5 -> 5e-7), and every
 # gradient is back inside the fp32 bound: worst 5.5e-6 at X = 160 (a norm weight,
 # floor 1.3e-6; r04s).  Bound: max(1e-5, 4 x the fp32 oracle's own floor).
 H3_GRAD_TOL = 1e-5

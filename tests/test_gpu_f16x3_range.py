@@ -137,7 +137,7 @@ def test_conv_f16x3_dgrad_unbiased():
     """The masked input-gradient launch (the backward's default accumulation mode,
     conv3d_f16x3.inc): the matrix core's accumulate truncates toward -inf, an
     offset of one sign for every output that a per-element NRMSE does not see but a
-    bias gradient's column sum over all voxels does (tools/dgrad_diag.py).  Bound:
+    bias gradient's column sum over all voxels does ("The truncation bias").  Bound:
     mean error / mean |ref| below 1e-8 (the uncancelled kernels sit at 5e-8 .. 1e-7),
     per-channel column sums within max(2e-6, 4 x PyTorch fp32's)."""
     K = _K()

@@ -72,7 +72,6 @@ def main():
     swin3D.set_compute_dtype(torch.float32)
     orig_split2, orig_pack, orig_conv, orig_wg = K.split2, K.conv_pack_f16x3, K.conv3d_f16x3, K.conv3d_wgrad_f16x3
     orig_k160 = K.gemm_k160_f16x3
-    orig_x6 = K.gemm_nt_x6
     src = {}        # planes data_ptr -> fp32 original (cpu)
     wts = {}        # packed data_ptr -> (w fp32 cpu, mode)
     report = []
@@ -152,21 +151,8 @@ def main():
         print(report[-1], flush=True)
         return r
 
-    def x6(A, B, Cm, M, N, Kd, lda, ldb):
-        c0 = Cm.detach().double().cpu().clone()
-        r = orig_x6(A, B, Cm, M, N, Kd, lda, ldb)
-        a, b = A.detach().reshape(M, Kd).cpu(), B.detach().reshape(N, Kd).cpu()
-        ref = a.double() @ b.double().t()
-        got = Cm.detach().double().cpu() - c0
-        t32 = (a @ b.t()).double()
-        report.append((f"x6 {M}x{N}x{Kd}", dict(total=rel(ref, got), bias=bias(ref, got), torch=rel(ref, t32),
-                                               a_max_over_rms=float(a.abs().max() / a.double().pow(2).mean().sqrt()))))
-        print(report[-1], flush=True)
-        return r
-
     K.split2, K.conv_pack_f16x3, K.conv3d_f16x3, K.conv3d_wgrad_f16x3 = split2, pack, conv, wgrad
     K.gemm_k160_f16x3 = k160
-    K.gemm_nt_x6 = x6
     seed = 71
     net = swin3D.SwinTransformer3DNet(num_swinblocks=1, in_chans=4, chans=160, kernel_size=3, window_size=(4, 4))
     net.eval()
