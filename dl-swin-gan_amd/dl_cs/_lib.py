@@ -136,6 +136,16 @@ SIGNATURES = {
     "dlcs_se_gate_bwd_workspace_bytes": [_I64, _I64, _I64],
     "dlcs_se_gate_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "dlcs_se_bwd_apply": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    # spatial gate of the CBAM-ResNet (cbam.hip)
+    "dlcs_cbam_chan_mean": [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
+    "dlcs_cbam_stencil5": [_P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _P],
+    "dlcs_cbam_stencil5_wgrad_workspace_bytes": [_I64, _I64, _I64, _I64],
+    "dlcs_cbam_stencil5_wgrad": [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _SZ, _P],
+    "dlcs_cbam_scale_res_relu": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_cbam_bwd_rowdot": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
+    "dlcs_cbam_bwd_reduce_workspace_bytes": [_I64, _I64, _I64, _I64, _I64],
+    "dlcs_cbam_bwd_reduce": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
+    "dlcs_cbam_bwd_apply": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
 }
 # DIAG build only (libdlcs_hip_diag.so: the superseded bf16 3-plane conv and NT GEMM);
 # bound when the loaded library has them

@@ -703,3 +703,66 @@ def se_bwd_apply(g, r_next, gate, dmean, B, N, C, dout=None):
     assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1]
     call("dlcs_se_bwd_apply", p(g), p(r_next), p(gate), p(dmean), p(dout), B, N, C, g.shape[-1], S())
     return dout
+
+
+# ---------------------------------------------------------------------------- CBAM spatial gate
+# fp32 rows [B D H W, ld] (patch-blocked) with C channels, dense maps [B, D, H, W]; dlcs.h "cbam.hip";
+# grid = (B, D, H, W)
+def cbam_chan_mean(o, gate, grid, C, out=None):
+    """a [B, D, H, W] = the channel mean of gate[b, c] o (dlcs_cbam_chan_mean)."""
+    if out is None:
+        out = empty(grid, torch.float32, o.device)
+    call("dlcs_cbam_chan_mean", p(o), p(gate), *grid, C, o.shape[-1], p(out), S())
+    return out
+
+
+def cbam_stencil5(x, w5, bias, grid, transposed=False, out=None):
+    """out = bias + w5 (5 x 5 x 5 cross-correlation, zero border) of the map x, or the
+    transposed form without bias (dlcs_cbam_stencil5)."""
+    if out is None:
+        out = empty(grid, torch.float32, x.device)
+    call("dlcs_cbam_stencil5", p(x), p(w5), None if transposed else p(bias), int(transposed), p(out), *grid, S())
+    return out
+
+
+def cbam_stencil5_wgrad(dq, a, grid, dw5, db5):
+    """dw5 += the 125 tap gradients of stencil5, db5 += sum dq (dlcs_cbam_stencil5_wgrad)."""
+    ws, nb = _ws("dlcs_cbam_stencil5_wgrad", dq.device, *grid)
+    call("dlcs_cbam_stencil5_wgrad", p(dq), p(a), *grid, p(dw5), p(db5), p(ws), nb, S())
+
+
+def cbam_scale_res_relu(o, gate, q, res, grid, C, out=None):
+    """out = relu(q[v] gate[b, c] o + res) (dlcs_cbam_scale_res_relu); out may be res, not o."""
+    if out is None:
+        out = empty(o.shape, torch.float32, o.device)
+    assert o.shape[-1] == res.shape[-1] == out.shape[-1]
+    call("dlcs_cbam_scale_res_relu", p(o), p(gate), p(q), p(res), p(out), *grid, C, o.shape[-1], S())
+    return out
+
+
+def cbam_bwd_rowdot(g, r_next, o, gate, grid, C, dq=None):
+    """dq [B, D, H, W] = sum_c g (r_next > 0) gate[b, c] o (dlcs_cbam_bwd_rowdot)."""
+    if dq is None:
+        dq = empty(grid, torch.float32, g.device)
+    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1]
+    call("dlcs_cbam_bwd_rowdot", p(g), p(r_next), p(o), p(gate), *grid, C, g.shape[-1], p(dq), S())
+    return dq
+
+
+def cbam_bwd_reduce(g, r_next, o, q, da, grid, C, dgate=None):
+    """dgate [B, C] = sum over a batch item's voxels of (g (r_next > 0) q + da / C) o (dlcs_cbam_bwd_reduce)."""
+    if dgate is None:
+        dgate = empty((grid[0], C), torch.float32, g.device)
+    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1]
+    ws, nb = _ws("dlcs_cbam_bwd_reduce", g.device, *grid, C)
+    call("dlcs_cbam_bwd_reduce", p(g), p(r_next), p(o), p(q), p(da), *grid, C, g.shape[-1], p(dgate), p(ws), nb, S())
+    return dgate
+
+
+def cbam_bwd_apply(g, r_next, gate, q, da, dmean, grid, C, dout=None):
+    """g *= (r_next > 0) in place; returns dout = (g q + da / C) gate[b, c] + dmean[b, c] (dlcs_cbam_bwd_apply)."""
+    if dout is None:
+        dout = empty(g.shape, torch.float32, g.device)
+    assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1]
+    call("dlcs_cbam_bwd_apply", p(g), p(r_next), p(gate), p(q), p(da), p(dmean), p(dout), *grid, C, g.shape[-1], S())
+    return dout

@@ -674,6 +674,54 @@ int dlcs_se_gate_bwd(const float* dgate, const float* gate, const float* hidden,
 int dlcs_se_bwd_apply(float* g, const float* r_next, const float* gate, const float* dmean, float* dout, int64_t B,
                       int64_t N, int64_t C, int64_t ld, dlcs_stream_t stream);
 
+/* ---- Spatial gate of the CBAM-ResNet (cbam.hip) -------------------------------------
+ * CBAM = dl_cs/models/CBAM.py: SABlock :425-475 (mean over channels -> Conv3d(1, 1, 5,
+ * padding 2), no sigmoid) applied to the channel-gated conv output of CBAMResBlock
+ * :517-521; the channel gate CABlock :371-422 is the SE gate above (dlcs_se_pool,
+ * dlcs_se_gate, dlcs_se_gate_bwd).  fp32.  Row operands are the patch-blocked rows
+ * [B N, ld] of a [B, D, H, W] grid with C channels, N = D H W, batch item b the rows
+ * [b N, (b + 1) N) and within it
+ *   row(t, y, x) = (((t/4) H/4 + y/4) W/4 + x/4) 64 + (t%4) 16 + (y%4) 4 + x%4;
+ * maps (a, q, dq, da) are dense [B, D, H, W].  gate [B, C] is the channel gate, w5 the
+ * 125 weights of the conv ([dt][dy][dx], a cross-correlation), bias its one bias.
+ * Row passes: D, H, W multiples of 4, 1 <= C <= 1024, B <= 65535; beyond,
+ * DLCS_ERR_UNSUPPORTED_SIZE and nothing is written.  The stencils take any D, H, W >= 1.
+ * Rows are accessed 16 B at a time when C % 4 == 0, ld % 4 == 0 and the row pointers
+ * are 16-B aligned, else one float at a time; columns [C, ld) are never read or written.
+ *
+ *   chan_mean:      a[b, v] = (1 / C) sum_c gate[b, c] o[v, c]
+ *   stencil5:       out[b, v] = bias + sum_d w5[d] in[b, v + d - 2], taps outside the
+ *                   grid read 0; transposed != 0: out[b, v] = sum_d w5[d] in[b, v - (d - 2)]
+ *                   (bias unused, may be NULL).  out may not alias in.
+ *   stencil5_wgrad: dw5[d] += sum_{b, v} dq[b, v] a[b, v + d - 2], db5[0] += sum dq
+ *   scale_res_relu: out = relu(q[v] gate[b, c] o + res); out may alias res, not o
+ *   bwd_rowdot:     dq[b, v] = sum_c g [r_next > 0] gate[b, c] o (dlcs_relu_grad's rule)
+ *   bwd_reduce:     dgate[b, c] = sum_v (g [r_next > 0] q[v] + da[v] / C) o
+ *   bwd_apply:      g <- g [r_next > 0] in place (bitwise dlcs_relu_grad),
+ *                   dout = (g q[v] + da[v] / C) gate[b, c] + dmean[b, c]; dout may not alias g
+ *
+ * stencil5_wgrad and bwd_reduce store per-workgroup partials in `workspace` and a
+ * second launch sums them in a fixed order: no float atomics, the same input gives the
+ * same bits.  Too small a workspace: DLCS_ERR_WORKSPACE before anything is launched.   */
+int dlcs_cbam_chan_mean(const float* o, const float* gate, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
+                        int64_t ld, float* map, dlcs_stream_t stream);
+int dlcs_cbam_stencil5(const float* in, const float* w5, const float* bias, int transposed, float* out, int64_t B,
+                       int64_t D, int64_t H, int64_t W, dlcs_stream_t stream);
+size_t dlcs_cbam_stencil5_wgrad_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W);
+int dlcs_cbam_stencil5_wgrad(const float* dq, const float* a, int64_t B, int64_t D, int64_t H, int64_t W, float* dw5,
+                             float* db5, void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_cbam_scale_res_relu(const float* o, const float* gate, const float* q, const float* res, float* out, int64_t B,
+                             int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, dlcs_stream_t stream);
+int dlcs_cbam_bwd_rowdot(const float* g, const float* r_next, const float* o, const float* gate, int64_t B, int64_t D,
+                         int64_t H, int64_t W, int64_t C, int64_t ld, float* dq, dlcs_stream_t stream);
+size_t dlcs_cbam_bwd_reduce_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int64_t C);
+int dlcs_cbam_bwd_reduce(const float* g, const float* r_next, const float* o, const float* q, const float* da, int64_t B,
+                         int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, float* dgate, void* workspace,
+                         size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_cbam_bwd_apply(float* g, const float* r_next, const float* gate, const float* q, const float* da,
+                        const float* dmean, float* dout, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld,
+                        dlcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,7 +105,8 @@ def reconstruct(model_by_dev, transform_by_dev, dataset, batch_size):
     return np.stack(out)
 
 
-def main(args):
+def main(args, builder=None):
+    """builder: the config -> model function (default: build_model above)."""
     from dl_cs.data.preprocess import DataTransform
     from dl_cs.models import swin3D
     swin3D.set_compute_dtype(torch.bfloat16 if args.dtype == 'bf16' else torch.float32)
@@ -124,7 +125,7 @@ def main(args):
     config = load_cfg(args.config_file)
     model_by_dev, tf_by_dev = {}, {}
     for d in devices:
-        m = build_model(config)
+        m = (builder or build_model)(config)
         checkpoint.load_model(m, args.ckpt)
         m.eval()
         for p in m.parameters():                                            # freeze()

@@ -124,7 +124,7 @@ class Trainer:
         self.cfg, self.args, self.rank, self.world, self.device = config, args, rank, world, device
         swin3D.set_compute_dtype(torch.bfloat16 if args.dtype == 'bf16' else torch.float32)
         torch.manual_seed(config.SEED)
-        self.model = build_model(config).to(device)
+        self.model = (getattr(args, 'builder', None) or build_model)(config).to(device)
         if world > 1:
             broadcast_parameters(self.model, 0)
         self.opt = optim.adam([p for p in self.model.parameters() if p.requires_grad], lr=config.OPTIMIZER.ADAM.LR)
@@ -313,8 +313,12 @@ def create_arg_parser():
     return p
 
 
-def main(argv=None):
-    main_args(create_arg_parser().parse_args(argv))
+def main(argv=None, builder=None):
+    """builder: the config -> model function the trainer uses (default: build_model above)."""
+    args = create_arg_parser().parse_args(argv)
+    if builder is not None:
+        args.builder = builder
+    main_args(args)
 
 
 def main_args(args):
