@@ -3,7 +3,7 @@
 
 Same classes, constructor arguments and state_dict keys as the reference
 (r3d = dl_cs/models/resnet3d.py:163-317).  The whole network runs as one HIP
-autograd node (_ResNetFn) on the generic Conv3d k3 kernels (dlcs_conv3d_k3 /
+autograd node (_TrunkFn) on the generic Conv3d k3 kernels (dlcs_conv3d_k3 /
 dlcs_conv3d_k3_wgrad, any channel count padded to 32) in the patch-blocked
 channels-last layout of the Swin path.
 
@@ -58,6 +58,14 @@ def _wgrad(x, cin, g, cout, grid, gw, gb, rows):
     K.colsum(g, gb, rows=rows, C=cout, ld=g.shape[-1])
 
 
+def _capture(r, ts, grid, F):
+    """Test hook: the ReLU decisions [r0, t0, r1, t1, ..., r_L] in the oracle's call order."""
+    from . import engine
+    if engine.CAPTURE is not None:
+        order = [t for k in range(len(ts)) for t in (r[k], ts[k])] + [r[-1]]
+        engine.CAPTURE.append(dict(relu_inputs=order, grid=grid, C=F))
+
+
 def resnet_forward(P, names, x, nblocks, pad):
     """x complex64 [B, E, T, Y, X] -> (out complex64, saved)."""
     B, E, T, Y, X = x.shape
@@ -78,10 +86,7 @@ def resnet_forward(P, names, x, nblocks, pad):
     o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u,
               out_dtype=torch.float32)
     out = K.swin_post(o, (B, E, T, Y, X), pad)
-    from . import engine
-    if engine.CAPTURE is not None:                   # test hook: ReLU decisions in the oracle's call order
-        order = [t for k in range(nblocks) for t in (r[k], ts[k])] + [r[-1]]
-        engine.CAPTURE.append(dict(relu_inputs=order, grid=grid, C=F))
+    _capture(r, ts, grid, F)
     return out, dict(u=u, r=r, ts=ts, grid=grid, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
 
 
@@ -108,11 +113,75 @@ def resnet_backward(P, names, sv, gout, grads):
     return K.swin_pre_bwd(du, sv["shape"], pad)
 
 
-class _ResNetFn(torch.autograd.Function):
+def gated_forward(P, names, x, nblocks, pad, gate):
+    """The trunk of the gated families (se3d.SeGate, CBAM.CbamGate), which keep conv_b's
+    output o_k un-activated and put a gate between it and the residual:
+
+        r_{k+1}, saved = gate.fwd(o_k, r_k, w, grid, F)        r_{k+1} = relu(gate(o_k) + r_k)
+
+    with w the block's gate parameters (names["blocks"][k][4:]) and saved whatever the
+    gate's backward needs besides o_k.  x complex64 [B, E, T, Y, X] -> (out complex64, saved)."""
+    B, E, T, Y, X = x.shape
+    Tp = T + 2 * pad
+    if Tp % 4 or Y % 4 or X % 4:
+        raise NotImplementedError("dl_cs HIP path: T+2*pad, Y and X must be multiples of 4")
+    grid = (B, Tp, Y, X)
+    cin = 2 * E
+    F = P[names["init_w"]].shape[0]
+    u = K.swin_pre(x.contiguous(), torch.float32, pad, PAD_CIN)
+    r = [_conv(u, cin, P[names["init_w"]], F, F, grid, bias=P[names["init_b"]], relu_out=1)]
+    ts, os_, gs = [], [], []
+    for k in range(nblocks):
+        wa, ba, wb, bb, *w = (P[n] for n in names["blocks"][k])
+        t = _conv(r[-1], F, wa, F, F, grid, bias=ba, relu_out=1)
+        o = _conv(t, F, wb, F, F, grid, bias=bb)
+        r_next, saved = gate.fwd(o, r[-1], w, grid, F)
+        r.append(r_next); ts.append(t); os_.append(o); gs.append(saved)
+    o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u,
+              out_dtype=torch.float32)
+    out = K.swin_post(o, (B, E, T, Y, X), pad)
+    _capture(r, ts, grid, F)
+    return out, dict(u=u, r=r, ts=ts, os=os_, gs=gs, grid=grid, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
+
+
+def gated_backward(P, names, sv, gout, grads, gate):
+    """Backward of gated_forward.  Per block
+
+        do = gate.bwd(g, r_{k+1}, o_k, saved, w, gw, grid, F)
+
+    takes g = dL/dr_{k+1}, masks it in place into gz = g [r_{k+1} > 0] (the gradient of the
+    ReLU's argument, and so also the residual gradient into r_k), accumulates the gate
+    parameters' gradients into gw and returns conv_b's output gradient."""
+    grid, cin, F, pad = sv["grid"], sv["cin"], sv["F"], sv["pad"]
+    rows = grid[0] * grid[1] * grid[2] * grid[3]
+    r, ts, u = sv["r"], sv["ts"], sv["u"]
+    go = K.swin_post_bwd(gout.contiguous(), torch.float32, pad, PAD_CIN)           # dL/d out (and the + u path)
+    # final layer: out = conv_f(r_L) + b_f + u
+    _wgrad(r[-1], F, go, cin, grid, grads[names["final_w"]], grads[names["final_b"]], rows)
+    g = _dgrad(go, cin, P[names["final_w"]], F, F, grid)                            # dL/d r_L
+    for k in reversed(range(len(ts))):
+        wa, ba, wb, bb, *w = (P[n] for n in names["blocks"][k])
+        gwa, gba, gwb, gbb, *gw = (grads[n] for n in names["blocks"][k])
+        # r_{k+1} = relu(gate(o) + r_k), o = conv_b(t_k) + b_b, t_k = relu(conv_a(r_k) + b_a)
+        do = gate.bwd(g, r[k + 1], sv["os"][k], sv["gs"][k], w, gw, grid, F)        # g is now gz
+        _wgrad(ts[k], F, do, F, grid, gwb, gbb, rows)
+        gt = _dgrad(do, F, wb, F, F, grid, mask=ts[k])
+        _wgrad(r[k], F, gt, F, grid, gwa, gba, rows)
+        g = _dgrad(gt, F, wa, F, F, grid, res=g)                                    # dL/d r_k (conv + residual)
+    g = K.relu_grad(g, r[0])                                                        # dL/d o_0
+    # init layer: o_0 = conv0(u) + b0 ;  du = conv0^T(g) + go (the final residual)
+    _wgrad(u, cin, g, F, grid, grads[names["init_w"]], grads[names["init_b"]], rows)
+    du = _dgrad(g, F, P[names["init_w"]], cin, PAD_CIN, grid, res=go, out_dtype=torch.float32)
+    return K.swin_pre_bwd(du, sv["shape"], pad)
+
+
+class _TrunkFn(torch.autograd.Function):
+    """One node per regularizer call; meta["trunk"] is the family's (forward, backward) pair."""
+
     @staticmethod
     def forward(ctx, x, meta, *plist):
         P = dict(zip(meta["order"], plist))
-        out, sv = resnet_forward(P, meta["names"], x.to(torch.complex64), meta["nblocks"], meta["pad"])
+        out, sv = meta["trunk"][0](P, meta["names"], x.to(torch.complex64), meta["nblocks"], meta["pad"])
         ctx.state = (P, sv, meta)
         return out
 
@@ -120,45 +189,76 @@ class _ResNetFn(torch.autograd.Function):
     def backward(ctx, gout):
         P, sv, meta = ctx.state
         grads = {n: torch.zeros_like(p) for n, p in P.items()}
-        gx = resnet_backward(P, meta["names"], sv, gout.to(torch.complex64), grads)
+        gx = meta["trunk"][1](P, meta["names"], sv, gout.to(torch.complex64), grads)
         ctx.state = None
         return (gx, None) + tuple(grads[n] for n in meta["order"])
 
 
-class ResNet(nn.Module):
-    """r3d:243-317 -- init ConvBlock (no activation), num_resblocks ResBlocks,
-    final pre-activation ConvBlock back to in_chans, plus the input residual."""
+def _wb(pre):
+    return f"{pre}.weight", f"{pre}.bias"
 
-    def __init__(self, num_resblocks, in_chans, chans, kernel_size, act_type='relu', use_complex_layers=False,
-                 circular_pad=True):
+
+class _TrunkNet(nn.Module):
+    """What ResNet, se3d.SeResNet and CBAM.CBAMResNet share: init ConvBlock (no activation),
+    num_resblocks blocks, final pre-activation ConvBlock back to in_chans, plus the input
+    residual (r3d:243-317).  A family supplies the five names below, its own __init__
+    signature (rr is the gated families' hidden width) and _block_keys(b): the parameter keys
+    of the block at prefix b, conv_a's and conv_b's weight and bias, then the gate's."""
+    NAME = None        # the family, as the messages call it
+    CONFIG = None      # the config file they cite
+    BLOCK = None       # block class
+    BLOCKS = None      # attribute (and state_dict prefix) of the block list
+    TRUNK = None       # (forward, backward) for _TrunkFn
+
+    def __init__(self, num_resblocks, in_chans, chans, kernel_size, act_type, use_complex_layers, circular_pad,
+                 rr=None):
         super().__init__()
+        head = f"dl_cs HIP {self.NAME}:"
         if use_complex_layers:
-            raise NotImplementedError("dl_cs HIP ResNet: COMPLEX: False (configs/example.yaml)")
+            raise NotImplementedError(f"{head} COMPLEX: False ({self.CONFIG})")
         if kernel_size != 3 or act_type != 'relu' or not circular_pad:
-            raise NotImplementedError("dl_cs HIP ResNet: kernel 3, relu, circular pad (configs/example.yaml)")
+            raise NotImplementedError(f"{head} kernel 3, relu, circular pad ({self.CONFIG})")
+        if rr is not None and not (1 <= chans <= 1024 and 1 <= rr <= 256):
+            raise NotImplementedError(f"{head} 1 <= NUM_FEATURES <= 1024, 1 <= RR <= 256 (dlcs_se_gate)")
         self.use_complex_layers = use_complex_layers
         self.circular_pad = circular_pad
-        self.pad_size = (2 * num_resblocks + 2) * (kernel_size - 1) // 2                  # r3d:253
+        self.pad_size = (2 * num_resblocks + 2) * (kernel_size - 1) // 2      # r3d:253, se3d:454, CBAM:578
+        gate_args = () if rr is None else (rr,)
         self.init_layer = ConvBlock(in_chans, chans, kernel_size, act_type='none')
-        self.res_blocks = nn.ModuleList([ResBlock(chans, kernel_size, act_type=act_type)
-                                         for _ in range(num_resblocks)])
+        setattr(self, self.BLOCKS, nn.ModuleList([self.BLOCK(chans, kernel_size, *gate_args, act_type=act_type)
+                                                  for _ in range(num_resblocks)]))
         self.final_layer = ConvBlock(chans, in_chans, kernel_size, act_type=act_type)
 
-    def _names(self):
-        c = lambda pre: (f"{pre}.layers.2.conv.weight", f"{pre}.layers.2.conv.bias")
-        blocks = []
-        for k in range(len(self.res_blocks)):
-            blocks.append(c(f"res_blocks.{k}.layers.0") + c(f"res_blocks.{k}.layers.1"))
-        iw, ib = c("init_layer")
-        fw, fb = c("final_layer")
-        return dict(init_w=iw, init_b=ib, final_w=fw, final_b=fb, blocks=blocks)
+    @staticmethod
+    def c(pre):
+        """Weight and bias keys of the ConvBlock at pre."""
+        return _wb(f"{pre}.layers.2.conv")
 
     def forward(self, input):
         if get_compute_dtype() != torch.float32:
-            raise NotImplementedError("dl_cs HIP ResNet: fp32 (the generic conv kernels; no bf16 wgrad at 64 ch)")
+            raise NotImplementedError(f"dl_cs HIP {self.NAME}: fp32 (the generic conv kernels; no bf16 wgrad at 64 ch)")
         if not input.is_cuda:
-            raise RuntimeError("dl_cs HIP ResNet needs GPU tensors (no CPU fallback in the product path)")
+            raise RuntimeError(f"dl_cs HIP {self.NAME} needs GPU tensors (no CPU fallback in the product path)")
         params = dict(self.named_parameters())
         order = list(params.keys())
-        meta = dict(order=order, names=self._names(), nblocks=len(self.res_blocks), pad=self.pad_size)
-        return _ResNetFn.apply(input, meta, *[params[n] for n in order])
+        nblocks = len(getattr(self, self.BLOCKS))
+        (iw, ib), (fw, fb) = self.c("init_layer"), self.c("final_layer")
+        names = dict(init_w=iw, init_b=ib, final_w=fw, final_b=fb,
+                     blocks=[self._block_keys(f"{self.BLOCKS}.{k}") for k in range(nblocks)])
+        meta = dict(order=order, names=names, nblocks=nblocks, pad=self.pad_size, trunk=self.TRUNK)
+        return _TrunkFn.apply(input, meta, *[params[n] for n in order])
+
+
+class ResNet(_TrunkNet):
+    """r3d:243-317 -- init ConvBlock (no activation), num_resblocks ResBlocks,
+    final pre-activation ConvBlock back to in_chans, plus the input residual."""
+    NAME, CONFIG, BLOCK, BLOCKS = "ResNet", "configs/example.yaml", ResBlock, "res_blocks"
+    TRUNK = (resnet_forward, resnet_backward)
+
+    def __init__(self, num_resblocks, in_chans, chans, kernel_size, act_type='relu', use_complex_layers=False,
+                 circular_pad=True):
+        super().__init__(num_resblocks, in_chans, chans, kernel_size, act_type, use_complex_layers, circular_pad)
+
+    def _block_keys(self, b):
+        return self.c(f"{b}.layers.0") + self.c(f"{b}.layers.1")
+

@@ -71,8 +71,10 @@ def _dc_step(A, x, ATy, step_size):
     return x + step_size * (A(A(x), adjoint=True) - ATy)
 
 
-class ProximalGradientDescent(UnrolledSwinNet):
-    """urs:77-122 -- unrolled PGD: x <- R_i(x + s (A^H A x - A^H y)), s = -2 fixed."""
+class PGDSteps:
+    """Mixin in front of an unrolled base (this module's, unrolled.py's, unrolledSE.py's,
+    unrolledCBAM.py's) that sets num_unrolls, cnn_update, fix_step_size and do_checkpoint:
+    x <- R_i(x + s (A^H A x - A^H y)), s = -2 (learnable unless FIX_STEP_SIZE)."""
 
     def __init__(self, config):
         super().__init__(config)
@@ -99,9 +101,14 @@ class ProximalGradientDescent(UnrolledSwinNet):
         return xi
 
 
-class HalfQuadraticSplitting(UnrolledSwinNet):
-    """urs:125-172 -- HQS / MoDL with a conjugate-gradient data-consistency solve
-    (the normal operator runs on the HIP SENSE kernels)."""
+class ProximalGradientDescent(PGDSteps, UnrolledSwinNet):
+    """urs:77-122 -- unrolled PGD, s = -2 fixed."""
+
+
+class HQSSteps:
+    """Mixin like PGDSteps: z = R_i(x); x <- CG(A^H A + lamda I, A^H y + lamda z), HQS / MoDL
+    with a conjugate-gradient data-consistency solve (the normal
+    operator runs on the HIP SENSE kernels)."""
 
     def __init__(self, config):
         super().__init__(config)
@@ -145,3 +152,7 @@ class HalfQuadraticSplitting(UnrolledSwinNet):
             else:
                 xi = update(i)(xi)
         return xi
+
+
+class HalfQuadraticSplitting(HQSSteps, UnrolledSwinNet):
+    """urs:125-172"""
