@@ -146,6 +146,12 @@ SIGNATURES = {
     "dlcs_cbam_bwd_reduce_workspace_bytes": [_I64, _I64, _I64, _I64, _I64],
     "dlcs_cbam_bwd_reduce": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
     "dlcs_cbam_bwd_apply": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    # locally low-rank block operators of the DSLR family (lowrank.hip)
+    "dlcs_lr_extract": [_P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_lr_combine": [_P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_lr_compose": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_lr_project_l": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_lr_project_r": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
 }
 # DIAG build only (libdlcs_hip_diag.so: the superseded bf16 3-plane conv and NT GEMM);
 # bound when the loaded library has them

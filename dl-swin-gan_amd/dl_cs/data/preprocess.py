@@ -6,7 +6,10 @@ CinePreprocess turns one fully-sampled slice (k-space [C, T, Y, X], ESPIRiT maps
 (masked k-space, mask, maps, initial image, scale, target) exactly as the
 reference does: FFT-domain crop / flip augmentation, SENSE-adjoint target,
 VDkt undersampling, 95th-percentile scaling from the time-averaged image, and
-the sliding-window initial guess (pp:54-180).
+the sliding-window initial guess (pp:54-180).  With lr_decom=True (the DSLR
+family, pp:166-178) the initial image is also factored into its locally
+low-rank block factors and the tuple is (masked k-space, mask, maps, L_init,
+R_init, initial image, scale, target); the truncated SVD runs on the host.
 
 With device='cuda' every per-voxel step runs on the GPU through libdlcs_hip --
 dlcs_fft2 (augmentation round trip), dlcs_crop_flip, dlcs_sense_adj (target,
@@ -22,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..mri import lowrank as lr
 from ..mri import subsample as ss
 from ..mri import transforms as T
 from ..mri import utils
@@ -96,8 +100,10 @@ class CinePreprocess(Preprocess):
 
     def __init__(self, config, lr_decom=False, use_seed=False, device=None):
         super().__init__(config, use_seed)
+        self.lr_decom = lr_decom                                            # pp:48-52
         if lr_decom:
-            raise NotImplementedError("DSLR low-rank decomposition is not on the Swin path")
+            D = config.MODEL.PARAMETERS.DSLR
+            self.block_size, self.num_basis, self.overlapping = D.BLOCK_SIZE, D.NUM_BASIS, D.OVERLAPPING
         us = config.AUG_TRAIN.UNDERSAMPLE
         self.mask_func = ss.VDktMaskFunc(us.ACCELERATIONS, sim_partial_kx=us.PARTIAL_KX,
                                          sim_partial_ky=us.PARTIAL_KY)
@@ -152,6 +158,10 @@ class CinePreprocess(Preprocess):
         init = utils.sliding_window(masked, dim=2, window_size=5) if self.config.MODEL.PARAMETERS.SLWIN_INIT \
             else masked                                                     # pp:160-163
         init_image = A(init, adjoint=True)
+        if self.lr_decom:                                                   # pp:166-178
+            decompose = lr.Decompose(self.block_size, self.num_basis, list(target.shape), overlapping=self.overlapping)
+            L_init, R_init = decompose(init_image)
+            return masked[0], mask[0], maps[0], L_init, R_init, init_image[0], scale, target[0]
         return masked[0], mask[0], maps[0], init_image[0], scale, target[0]
 
 

@@ -60,7 +60,10 @@ class GradBuckets:
         self.armed = True
         self.index, self.uses, self.seen, self.views = {}, {}, {}, {}
         nets = []
-        regs = model.cnn_update if hasattr(model, "cnn_update") else model.nn_update      # Swin / ResNet, DiT
+        if hasattr(model, "bucket_nets"):                                                 # DSLR: two lists of networks
+            regs = model.bucket_nets()
+        else:
+            regs = model.cnn_update if hasattr(model, "cnn_update") else model.nn_update  # Swin / ResNet, DiT
         for net in regs:
             if id(net) not in self.index:
                 self.index[id(net)] = len(nets)

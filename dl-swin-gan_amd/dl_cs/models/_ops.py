@@ -766,3 +766,93 @@ def cbam_bwd_apply(g, r_next, gate, q, da, dmean, grid, C, dout=None):
     assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1]
     call("dlcs_cbam_bwd_apply", p(g), p(r_next), p(gate), p(q), p(da), p(dmean), p(dout), *grid, C, g.shape[-1], S())
     return dout
+
+
+# ---------------------------------------------------------------------------- low-rank blocks (DSLR)
+LR_BLOCKS = (4, 8, 16)
+LR_MAX_E, LR_MAX_T, LR_MAX_R = 2, 32, 8
+
+
+def lr_check(E, T, b, r=1):
+    """The supported range of the dlcs_lr_* kernels (dlcs.h); beyond it there is no fallback."""
+    if b not in LR_BLOCKS or not 1 <= E <= LR_MAX_E or not 1 <= T <= LR_MAX_T or not 1 <= r <= LR_MAX_R:
+        raise NotImplementedError(f"low-rank block kernels: block size {b}, E {E}, T {T}, rank {r} outside "
+                                  f"b in {LR_BLOCKS}, E <= {LR_MAX_E}, T <= {LR_MAX_T}, r <= {LR_MAX_R}")
+
+
+def lr_num_blocks(Y, X, b):
+    """N of the kernels' geometry (dlcs.h): (2 (Y / b + 1) - 1) (2 (X / b + 1) - 1)."""
+    return (2 * (Y // b + 1) - 1) * (2 * (X // b + 1) - 1)
+
+
+def _lr_c64(weights, win, *tensors):
+    """The data tensors are contiguous complex64 and, like the operator's fp32 window and
+    weights (which the kernels read through raw pointers), on the GPU."""
+    for t in tensors:
+        if t.dtype != torch.complex64 or not t.is_contiguous():
+            raise _lib.DlcsError("low-rank block kernels take contiguous complex64 tensors")
+    for t in (weights, win):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.DlcsError("low-rank block kernels take a contiguous fp32 window and weights")
+    _lib.require_gpu(weights, win, *tensors)
+    if len({t.device for t in (weights, win) + tensors}) != 1:
+        raise _lib.DlcsError("low-rank block kernels: the operator's buffers and the data are on different GPUs")
+
+
+def lr_extract(image, weights, win, b, N, divide=False):
+    """blocks [N, E b^2, T] of image [E, T, Y, X] (dlcs_lr_extract)."""
+    E, T, Y, X = image.shape
+    lr_check(E, T, b)
+    _lr_c64(weights, win, image)
+    assert N == lr_num_blocks(Y, X, b), (N, image.shape, b)
+    out = empty((N, E * b * b, T), torch.complex64, image.device)
+    call("dlcs_lr_extract", p(image), p(weights), p(win), int(divide), p(out), E, T, Y, X, b, S())
+    return out
+
+
+def lr_combine(blocks, weights, win, b, shape, divide=True):
+    """image [E, T, Y, X] = shape from blocks [N, E b^2, T] (dlcs_lr_combine)."""
+    E, T, Y, X = shape
+    lr_check(E, T, b)
+    _lr_c64(weights, win, blocks)
+    assert blocks.shape == (lr_num_blocks(Y, X, b), E * b * b, T), (blocks.shape, shape, b)
+    out = empty((E, T, Y, X), torch.complex64, blocks.device)
+    call("dlcs_lr_combine", p(blocks), p(weights), p(win), int(divide), p(out), E, T, Y, X, b, S())
+    return out
+
+
+def lr_compose(L, R, weights, win, b, shape, divide=True):
+    """image [E, T, Y, X] = combine(L R^H) without the block tensor (dlcs_lr_compose)."""
+    E, T, Y, X = shape
+    r = L.shape[2]
+    lr_check(E, T, b, r)
+    _lr_c64(weights, win, L, R)
+    N = lr_num_blocks(Y, X, b)
+    assert L.shape == (N, E * b * b, r) and R.shape == (N, T, r), (L.shape, R.shape, shape, b)
+    out = empty((E, T, Y, X), torch.complex64, L.device)
+    call("dlcs_lr_compose", p(L), p(R), p(weights), p(win), int(divide), p(out), E, T, Y, X, b, r, S())
+    return out
+
+
+def lr_project_l(image, R, weights, win, b, divide=False):
+    """extract(image) R -> [N, E b^2, r] (dlcs_lr_project_l)."""
+    E, T, Y, X = image.shape
+    N, r = R.shape[0], R.shape[2]
+    lr_check(E, T, b, r)
+    _lr_c64(weights, win, image, R)
+    assert R.shape == (lr_num_blocks(Y, X, b), T, r), (R.shape, image.shape, b)
+    out = empty((N, E * b * b, r), torch.complex64, image.device)
+    call("dlcs_lr_project_l", p(image), p(R), p(weights), p(win), int(divide), p(out), E, T, Y, X, b, r, S())
+    return out
+
+
+def lr_project_r(image, L, weights, win, b, divide=False):
+    """extract(image)^H L -> [N, T, r] (dlcs_lr_project_r)."""
+    E, T, Y, X = image.shape
+    N, r = L.shape[0], L.shape[2]
+    lr_check(E, T, b, r)
+    _lr_c64(weights, win, image, L)
+    assert L.shape == (lr_num_blocks(Y, X, b), E * b * b, r), (L.shape, image.shape, b)
+    out = empty((N, T, r), torch.complex64, image.device)
+    call("dlcs_lr_project_r", p(image), p(L), p(weights), p(win), int(divide), p(out), E, T, Y, X, b, r, S())
+    return out

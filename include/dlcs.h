@@ -722,6 +722,40 @@ int dlcs_cbam_bwd_apply(float* g, const float* r_next, const float* gate, const 
                         const float* dmean, float* dout, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld,
                         dlcs_stream_t stream);
 
+/* ---- Locally low-rank block operators of the DSLR family (lowrank.hip) ---------------
+ * lowrank = dl_cs/mri/lowrank.py: ArrayToBlocks :13-187, Decompose.compose :247-253.
+ * complex64 data (interleaved re, im), fp32 window and weights, batch 1.
+ *   image   [E, T, Y, X]
+ *   blocks  [N, E b^2, T], row p = e b^2 + iy b + ix, block n = by nbx + bx
+ *   L       [N, E b^2, r],  R [N, T, r]
+ *   win     [b]: the periodic sqrt-Hann window (an element's factor is win[iy] win[ix])
+ *   weights [Y, X]: combine(extract(1)); read only when divide != 0 (else may be NULL)
+ * Geometry (lowrank:47-77): stride b / 2; padded sizes Yp = b (Y / b + 1), Xp likewise,
+ * left pad (Yp - Y) / 2, the odd extra row or column on the right; nby = 2 Yp / b - 1,
+ * N = nby nbx; the crop takes rows [left pad, left pad + Y).
+ *   extract:   blocks = win unfold(pad(image)),   divide: image / (weights + 1e-8) first
+ *   combine:   image = crop(fold(win blocks)),    divide: then / (weights + 1e-8)
+ *              (divide 1 is lowrank's combine, divide 0 the exact adjoint of extract,
+ *              and combine(divide 1) is the adjoint of extract(divide 1))
+ *   compose:   image = combine(L R^H), the blocks never stored
+ *   project_l: out [N, E b^2, r] = extract(image) R
+ *   project_r: out [N, T, r]     = extract(image)^H L, the E b^2 rows of a block
+ *              reduced inside one workgroup
+ * Every sum runs in a fixed order without float atomics: the same input gives the same
+ * bits.  Supported: b in {4, 8, 16}, 1 <= E <= 2, 1 <= T <= 32, 1 <= r <= 8, any
+ * 1 <= Y, X <= 32768 (odd sizes included); beyond, DLCS_ERR_UNSUPPORTED_SIZE and nothing
+ * is written.  No workspace.  Outputs may not alias inputs.                             */
+int dlcs_lr_extract(const void* image, const float* weights, const float* win, int divide, void* blocks, int64_t E,
+                    int64_t T, int64_t Y, int64_t X, int64_t b, dlcs_stream_t stream);
+int dlcs_lr_combine(const void* blocks, const float* weights, const float* win, int divide, void* image, int64_t E,
+                    int64_t T, int64_t Y, int64_t X, int64_t b, dlcs_stream_t stream);
+int dlcs_lr_compose(const void* L, const void* R, const float* weights, const float* win, int divide, void* image,
+                    int64_t E, int64_t T, int64_t Y, int64_t X, int64_t b, int64_t r, dlcs_stream_t stream);
+int dlcs_lr_project_l(const void* image, const void* R, const float* weights, const float* win, int divide, void* out,
+                      int64_t E, int64_t T, int64_t Y, int64_t X, int64_t b, int64_t r, dlcs_stream_t stream);
+int dlcs_lr_project_r(const void* image, const void* L, const float* weights, const float* win, int divide, void* out,
+                      int64_t E, int64_t T, int64_t Y, int64_t X, int64_t b, int64_t r, dlcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

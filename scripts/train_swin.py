@@ -133,9 +133,9 @@ class Trainer:
         # the fused Swin backward writes straight into the buckets; other networks use hooks
         self.buckets = GradBuckets(self.model, world, direct=config.MODEL.MODEL_TYPE.upper() == 'SWIN')
         synth = tuple(args.synthetic_shape)
-        self.train_ds = make_dataset(config, args.data, 'train', CinePreprocess(config, use_seed=False, device=device),
+        self.train_ds = make_dataset(config, args.data, 'train', self.preprocess(CinePreprocess, False),
                                      args.synthetic_slices, synth)
-        self.val_ds = make_dataset(config, args.data, 'val', CinePreprocess(config, use_seed=True, device=device),
+        self.val_ds = make_dataset(config, args.data, 'val', self.preprocess(CinePreprocess, True),
                                    max(1, args.synthetic_slices // 4), synth)
         self.epoch, self.global_step = 0, 0
         self.best, self.best_path = float('inf'), None
@@ -143,6 +143,10 @@ class Trainer:
         self.log_path = os.path.join(self.out_dir, 'exp', 'metrics.jsonl')
         if rank == 0:
             os.makedirs(os.path.dirname(self.log_path), exist_ok=True)
+
+    def preprocess(self, cls, use_seed):
+        """The per-slice transform of the training (use_seed False) / validation set."""
+        return cls(self.cfg, use_seed=use_seed, device=self.device)
 
     # ---------------------------------------------------------------- state
     def resume(self, path):
@@ -281,6 +285,8 @@ def run(rank, world, args, devices, port=None):
     cls = Trainer
     if getattr(args, 'trainer', None) == 'gan':            # scripts/train_swin_gan.py
         from train_swin_gan import GanTrainer as cls
+    elif getattr(args, 'trainer', None) == 'lr':           # scripts/train_lr.py
+        from train_lr import LrTrainer as cls
     tr = cls(config, args, rank, world, device)
     if args.resume:
         if not args.ckpt:
