@@ -1,0 +1,219 @@
+// A box inside a padded grid: what lets the conv trunks of the ResNet, SE and CBAM
+// regularisers take any grid size.  fp32.
+//
+// The conv, SE and CBAM kernels work on the patch-blocked channels-last rows of a grid
+// (B, Dp, Hp, Wp) whose axes are multiples of 4.  A true grid ("box") (B, D, H, W),
+// D <= Dp, H <= Hp, W <= Wp, sits at the origin of that grid; the rows whose (t, y, x)
+// lies outside the box are "slack rows".  A k3 / pad-1 convolution on the padded grid
+// equals the zero-padded convolution on the box as long as every tensor a stencil or a
+// reduction reads is zero on the slack rows:
+//
+// * dlcs_box_pre / _pre_bwd / _post / _post_bwd -- dlcs_swin_pre / ... for a box: complex
+//   [B,E,T,Y,X] <-> real re | im channels, circular time pad (D = T + 2 pad), rows
+//   addressed in (Dp, Hp, Wp).  pre and post_bwd write every row of the padded grid
+//   (slack rows +0.0 in all ldc columns), pre_bwd and post read rows of the box only.
+// * dlcs_box_zero -- +0.0 into columns [0, C) of every slack row, nothing else touched.
+//   A batch item's slack rows are three disjoint slabs,
+//       t in [D, Dp)                                  (Dp - D) Hp Wp rows
+//       t in [0, D), y in [H, Hp)                     D (Hp - H) Wp rows
+//       t in [0, D), y in [0, H), x in [W, Wp)        D H (Wp - W) rows
+//   and the kernel enumerates exactly those: one thread per (slack row, column chunk),
+//   4 columns as one 16-B store when C % 4 == 0, ld % 4 == 0 and the base is 16-B
+//   aligned (se.hip's rule), else one float.  It reads no memory.
+#include "dlcs_common.h"
+
+namespace {
+
+// blocked offset of voxel (b, t, y, x) in a [B, Dp, Hp, Wp] grid (all multiples of 4)
+DLCS_DEV long box_row(int b, int t, int y, int x, int Dp, int Hp, int Wp) {
+    const int nT = Dp >> 2, nY = Hp >> 2, nX = Wp >> 2;
+    const long patch = (((long)b * nT + (t >> 2)) * nY + (y >> 2)) * nX + (x >> 2);
+    return patch * 64 + ((t & 3) << 4) + ((y & 3) << 2) + (x & 3);
+}
+
+struct BoxDims {
+    int B, E, Tn, Y, X, pad, Dp, Hp, Wp, ldc;
+};
+
+// u[b, t', y, x, c] = (c < E ? Re : Im) x[b, c mod E, (t' - pad) mod T, y, x] inside the box,
+// c < 2E; zero for c >= 2E and on slack rows.  POST_BWD: no wrap, zero for t' - pad outside [0, T).
+template <bool POST_BWD>
+__global__ void __launch_bounds__(256) box_scatter_kernel(const float2* x, float* u, BoxDims d) {
+    const int D = d.Tn + 2 * d.pad;
+    const long total = (long)d.B * d.Dp * d.Hp * d.Wp;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int xx = (int)(i % d.Wp);
+        long q = i / d.Wp;
+        const int y = (int)(q % d.Hp); q /= d.Hp;
+        const int tp = (int)(q % d.Dp);
+        const int b = (int)(q / d.Dp);
+        float* dst = u + box_row(b, tp, y, xx, d.Dp, d.Hp, d.Wp) * d.ldc;
+        bool in = tp < D && y < d.Y && xx < d.X;
+        int t = tp - d.pad;
+        if (POST_BWD) in = in && t >= 0 && t < d.Tn;
+        else t = (t % d.Tn + d.Tn) % d.Tn;
+        for (int c = 0; c < d.ldc; ++c) {
+            float v = 0.0f;
+            if (in && c < 2 * d.E) {
+                const int e = c % d.E;
+                const float2 z = x[((((long)b * d.E + e) * d.Tn + t) * d.Y + y) * d.X + xx];
+                v = (c < d.E) ? z.x : z.y;
+            }
+            dst[c] = v;
+        }
+    }
+}
+
+// PRE_BWD: gx[b, e, t] = sum over t' = t + pad + k T in [0, D) of g_u (circular-pad adjoint, the
+// order of dlcs_swin_pre_bwd); else out[b, e, t] = complex(o[c = e], o[c = E + e]) at t' = t + pad.
+template <bool PRE_BWD>
+__global__ void __launch_bounds__(256) box_gather_kernel(const float* o, float2* out, BoxDims d) {
+    const int D = d.Tn + 2 * d.pad;
+    const long total = (long)d.B * d.E * d.Tn * d.Y * d.X;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int xx = (int)(i % d.X);
+        long q = i / d.X;
+        const int y = (int)(q % d.Y); q /= d.Y;
+        const int t = (int)(q % d.Tn); q /= d.Tn;
+        const int e = (int)(q % d.E);
+        const int b = (int)(q / d.E);
+        if (PRE_BWD) {
+            float re = 0.0f, im = 0.0f;
+            for (int tp = (t + d.pad) % d.Tn; tp < D; tp += d.Tn) {
+                const float* src = o + box_row(b, tp, y, xx, d.Dp, d.Hp, d.Wp) * d.ldc;
+                re += src[e];
+                im += src[d.E + e];
+            }
+            out[i] = make_float2(re, im);
+        } else {
+            const float* src = o + box_row(b, t + d.pad, y, xx, d.Dp, d.Hp, d.Wp) * d.ldc;
+            out[i] = make_float2(src[e], src[d.E + e]);
+        }
+    }
+}
+
+struct ZeroDims {
+    int Dp, Hp, Wp, D, H, W;
+    long n1, n2, n3;        // rows of the three slack slabs of one batch item
+};
+
+// blockIdx.y = batch item; grid-stride over (slack row, column chunk) pairs of V columns
+template <int V>
+__global__ void __launch_bounds__(256) box_zero_kernel(float* x, long ld, int nch, ZeroDims z) {
+    const int b = blockIdx.y;
+    const long total = (z.n1 + z.n2 + z.n3) * nch;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int ch = (int)(i % nch);
+        long s = i / nch;
+        int t, y, xx;
+        if (s < z.n1) {                                   // t in [D, Dp), all y, all x
+            xx = (int)(s % z.Wp); s /= z.Wp;
+            y = (int)(s % z.Hp);
+            t = z.D + (int)(s / z.Hp);
+        } else if (s < z.n1 + z.n2) {                     // t in [0, D), y in [H, Hp), all x
+            s -= z.n1;
+            const int hs = z.Hp - z.H;
+            xx = (int)(s % z.Wp); s /= z.Wp;
+            y = z.H + (int)(s % hs);
+            t = (int)(s / hs);
+        } else {                                          // t in [0, D), y in [0, H), x in [W, Wp)
+            s -= z.n1 + z.n2;
+            const int ws = z.Wp - z.W;
+            xx = z.W + (int)(s % ws); s /= ws;
+            y = (int)(s % z.H);
+            t = (int)(s / z.H);
+        }
+        float* dst = x + box_row(b, t, y, xx, z.Dp, z.Hp, z.Wp) * ld + (long)ch * V;
+        if constexpr (V == 4) {
+            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            *reinterpret_cast<f32x4*>(dst) = v;
+        } else {
+            *dst = 0.0f;
+        }
+    }
+}
+
+unsigned box_blocks(long n) {
+    long g = (n + 255) / 256;
+    if (g > 8192) g = 8192;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
+
+// the padded grid holds the box, its axes are multiples of 4, every index the kernels form
+// in int fits and the row counts formed in long cannot overflow (2^40 rows per batch item
+// is beyond any memory)
+bool box_grid_ok(long Dp, long Hp, long Wp, long D, long H, long W) {
+    return Dp % 4 == 0 && Hp % 4 == 0 && Wp % 4 == 0 && D <= Dp && H <= Hp && W <= Wp &&
+           Dp < (1L << 30) && Hp < (1L << 30) && Wp < (1L << 30) && Dp * Hp <= (1L << 40) / Wp;
+}
+
+int box_dims(BoxDims* d, const void* a, const void* b, int64_t B, int64_t E, int64_t Tn, int64_t Y, int64_t X,
+             int64_t pad, int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc) {
+    DLCS_CHECK_ARG(a && b && B > 0 && E > 0 && Tn > 0 && Y > 0 && X > 0 && pad >= 0 && ldc >= 2 * E &&
+                   Tn < (1L << 30) && pad < (1L << 30));
+    if (!box_grid_ok(Dp, Hp, Wp, Tn + 2 * pad, Y, X) || B > (1L << 20) || E > (1L << 20) || B * E > (1L << 20) ||
+        ldc >= (1L << 30))
+        return DLCS_ERR_UNSUPPORTED_SIZE;
+    *d = BoxDims{(int)B, (int)E, (int)Tn, (int)Y, (int)X, (int)pad, (int)Dp, (int)Hp, (int)Wp, (int)ldc};
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dlcs_box_pre(const void* x, float* u, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                 int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
+    BoxDims d;
+    if (const int rc = box_dims(&d, x, u, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
+    hipLaunchKernelGGL(box_scatter_kernel<false>, dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0, (hipStream_t)stream,
+                       (const float2*)x, u, d);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_pre_bwd(const float* gu, void* gx, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                     int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
+    BoxDims d;
+    if (const int rc = box_dims(&d, gu, gx, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
+    hipLaunchKernelGGL(box_gather_kernel<true>, dim3(box_blocks(B * E * T * Y * X)), dim3(256), 0, (hipStream_t)stream,
+                       gu, (float2*)gx, d);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_post(const float* o, void* out, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                  int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
+    BoxDims d;
+    if (const int rc = box_dims(&d, o, out, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
+    hipLaunchKernelGGL(box_gather_kernel<false>, dim3(box_blocks(B * E * T * Y * X)), dim3(256), 0, (hipStream_t)stream,
+                       o, (float2*)out, d);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_post_bwd(const void* gout, float* go, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                      int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
+    BoxDims d;
+    if (const int rc = box_dims(&d, gout, go, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
+    hipLaunchKernelGGL(box_scatter_kernel<true>, dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0, (hipStream_t)stream,
+                       (const float2*)gout, go, d);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_zero(float* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_t Hp, int64_t Wp, int64_t D, int64_t H,
+                  int64_t W, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(x && B > 0 && C > 0 && ld >= C && D > 0 && H > 0 && W > 0);
+    if (!box_grid_ok(Dp, Hp, Wp, D, H, W) || B > 65535 || C >= (1L << 30)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    ZeroDims z{(int)Dp, (int)Hp, (int)Wp, (int)D, (int)H, (int)W, (Dp - D) * Hp * Wp, D * (Hp - H) * Wp, D * H * (Wp - W)};
+    const long n = z.n1 + z.n2 + z.n3;
+    if (n == 0) return 0;
+    const bool vec = C % 4 == 0 && ld % 4 == 0 && al16(x);
+    const int nch = (int)(vec ? C / 4 : C);
+    const dim3 grid(box_blocks(n * nch), (unsigned)B);
+    if (vec)
+        hipLaunchKernelGGL(box_zero_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
+    else
+        hipLaunchKernelGGL(box_zero_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
+    return dlcs_launch_status();
+}
+
+}  // extern "C"

@@ -105,6 +105,12 @@ SIGNATURES = {
     "dlcs_swin_pre_bwd": [_INT, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_swin_post": [_INT, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_swin_post_bwd": [_INT, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    # a box inside a padded grid (box.hip)
+    "dlcs_box_pre": [_P, _P] + [_I64] * 10 + [_P],
+    "dlcs_box_pre_bwd": [_P, _P] + [_I64] * 10 + [_P],
+    "dlcs_box_post": [_P, _P] + [_I64] * 10 + [_P],
+    "dlcs_box_post_bwd": [_P, _P] + [_I64] * 10 + [_P],
+    "dlcs_box_zero": [_P] + [_I64] * 9 + [_P],
     "dlcs_axpby": [_INT, _INT, _P, _P, _I64, _F, _F, _P],
     "dlcs_relu_grad": [_INT, _P, _INT, _P, _I64, _P],
     "dlcs_permute": [_INT, _INT, _P, _P, _I64, _P, _P, _INT, _P],

@@ -35,6 +35,7 @@ from torch import nn
 
 from . import _ops as K
 from .resnet3d import _TrunkNet, _wb, gated_backward, gated_forward
+from .se3d import SeGate
 from .swin3D import Activation, ConvBlock, Conv3d
 
 _FUSED = "dl_cs: runs inside CBAMResNet's fused HIP node"
@@ -133,23 +134,23 @@ class CbamGate:
     and gw their gradients, saved = (m, h, s, a, q); the equations are in the module docstring."""
 
     @staticmethod
-    def fwd(o, r_prev, w, grid, F):
+    def fwd(o, r_prev, w, grid, F, N):
         w1, b1, w2, b2, w5, b5 = w
-        m = K.se_pool(o, grid[0], grid[1] * grid[2] * grid[3], F)
+        m = SeGate.pool(o, grid, F, N)
         h, s = K.se_gate(m, w1, b1, w2, b2)
         a = K.cbam_chan_mean(o, s, grid, F)
         q = K.cbam_stencil5(a, w5, b5, grid)
         return K.cbam_scale_res_relu(o, s, q, r_prev, grid, F), (m, h, s, a, q)
 
     @staticmethod
-    def bwd(g, r_next, o, saved, w, gw, grid, F):
+    def bwd(g, r_next, o, saved, w, gw, grid, F, N):
         (m, h, s, a, q), (w1, _, w2, _, w5, _) = saved, w
         gw1, gb1, gw2, gb2, gw5, gb5 = gw
         dq = K.cbam_bwd_rowdot(g, r_next, o, s, grid, F)
         K.cbam_stencil5_wgrad(dq, a, grid, gw5, gb5)
         da = K.cbam_stencil5(dq, w5, None, grid, transposed=True)
         ds = K.cbam_bwd_reduce(g, r_next, o, q, da, grid, F)
-        dm = K.se_gate_bwd(ds, s, h, m, w1, w2, 1.0 / (grid[1] * grid[2] * grid[3]), gw1, gb1, gw2, gb2)
+        dm = K.se_gate_bwd(ds, s, h, m, w1, w2, 1.0 / N, gw1, gb1, gw2, gb2)
         return K.cbam_bwd_apply(g, r_next, s, q, da, dm, grid, F)                   # g is now gz
 
 

@@ -634,6 +634,48 @@ def swin_post_bwd(gout, dtype, pad, ldc):
     return go
 
 
+# ---------------------------------------------------------------------------- box in a padded grid
+# fp32; grid = (B, Dp, Hp, Wp) multiples of 4, the box (B, T + 2 pad, Y, X) at its origin; dlcs.h "box.hip"
+def pad4(n):
+    return (n + 3) // 4 * 4
+
+
+def box_pre(x, pad, ldc, grid):
+    """swin_pre into the rows of the padded grid; slack rows zero."""
+    B, E, T, Y, X = x.shape
+    u = empty((grid[0] * grid[1] * grid[2] * grid[3], ldc), torch.float32, x.device)
+    call("dlcs_box_pre", p(x), p(u), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], ldc, S())
+    return u
+
+
+def box_pre_bwd(gu, shape, pad, grid):
+    B, E, T, Y, X = shape
+    gx = empty(shape, torch.complex64, gu.device)
+    call("dlcs_box_pre_bwd", p(gu), p(gx), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], gu.shape[-1], S())
+    return gx
+
+
+def box_post(o, shape, pad, grid):
+    B, E, T, Y, X = shape
+    out = empty(shape, torch.complex64, o.device)
+    call("dlcs_box_post", p(o), p(out), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], o.shape[-1], S())
+    return out
+
+
+def box_post_bwd(gout, pad, ldc, grid):
+    """swin_post_bwd into the rows of the padded grid; slack rows zero."""
+    B, E, T, Y, X = gout.shape
+    go = empty((grid[0] * grid[1] * grid[2] * grid[3], ldc), torch.float32, gout.device)
+    call("dlcs_box_post_bwd", p(gout), p(go), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], ldc, S())
+    return go
+
+
+def box_zero(x, C, grid, box):
+    """x[slack rows, :C] = +0.0 in place (x fp32 [rows of grid, ld]); box = (B, D, H, W)."""
+    call("dlcs_box_zero", p(x), x.shape[-1], C, *grid, *box[1:], S())
+    return x
+
+
 def relu_grad(g, a):
     """g *= (a > 0) in place (a: stored post-ReLU activation, same element count)."""
     assert g.numel() == a.numel()

@@ -58,43 +58,89 @@ def _wgrad(x, cin, g, cout, grid, gw, gb, rows):
     K.colsum(g, gb, rows=rows, C=cout, ld=g.shape[-1])
 
 
-def _capture(r, ts, grid, F):
-    """Test hook: the ReLU decisions [r0, t0, r1, t1, ..., r_L] in the oracle's call order."""
+def _capture(r, ts, grid, F, box):
+    """Test hook: the ReLU decisions [r0, t0, r1, t1, ..., r_L] in the oracle's call order
+    (on the padded path in the padded grid's rows, with the box beside it)."""
     from . import engine
     if engine.CAPTURE is not None:
         order = [t for k in range(len(ts)) for t in (r[k], ts[k])] + [r[-1]]
-        engine.CAPTURE.append(dict(relu_inputs=order, grid=grid, C=F))
+        entry = dict(relu_inputs=order, grid=grid, C=F)
+        if box is not None:
+            entry["box"] = box
+        engine.CAPTURE.append(entry)
+
+
+# Any grid size.  The kernels take grids whose axes are multiples of 4, so a call whose true
+# grid ("box") (B, T + 2 pad, Y, X) is not one runs on the grid rounded up ("padded path").
+# The rows outside the box are slack rows; the conv on the padded grid is the reference's
+# zero-padded conv on the box as long as every tensor a conv (forward, dgrad, wgrad), colsum,
+# the gates' pool / channel mean / stencil or a backward reduce reads is zero there.  box_pre
+# and box_post_bwd write zeros there, a masked dgrad and relu_grad give zeros wherever the
+# stored post-ReLU tensor is zero, and box_post / box_pre_bwd read the box only; what is left
+# are the tensors that a bias (forward) or dmean / da (gate backward) makes non-zero on slack
+# rows, which _zero clears: r0, t, r_{k+1} (plain trunk) or conv_b's output o (gated trunk)
+# in the forward, the gate backward's dout in the backward.  Without slack box is None and
+# the launches are the unpadded ones.
+def _pre(x, pad):
+    """x complex64 [B, E, T, Y, X] -> (u, grid, box): grid the (padded) grid of u's rows."""
+    B, E, T, Y, X = x.shape
+    box = (B, T + 2 * pad, Y, X)
+    grid = (B,) + tuple(K.pad4(n) for n in box[1:])
+    if grid == box:
+        return K.swin_pre(x.contiguous(), torch.float32, pad, PAD_CIN), grid, None
+    return K.box_pre(x.contiguous(), pad, PAD_CIN, grid), grid, box
+
+
+def _post(o, shape, pad, grid, box):
+    return K.swin_post(o, shape, pad) if box is None else K.box_post(o, shape, pad, grid)
+
+
+def _post_bwd(gout, pad, grid, box):
+    if box is None:
+        return K.swin_post_bwd(gout.contiguous(), torch.float32, pad, PAD_CIN)
+    return K.box_post_bwd(gout.contiguous(), pad, PAD_CIN, grid)
+
+
+def _pre_bwd(du, shape, pad, grid, box):
+    return K.swin_pre_bwd(du, shape, pad) if box is None else K.box_pre_bwd(du, shape, pad, grid)
+
+
+def _zero(t, C, grid, box):
+    """t with its slack rows cleared in place (nothing to do without slack)."""
+    return t if box is None else K.box_zero(t, C, grid, box)
+
+
+def _nvox(grid, box):
+    """Voxels per batch item that the gates' means run over: the box's, not the padded grid's."""
+    g = grid if box is None else box
+    return g[1] * g[2] * g[3]
 
 
 def resnet_forward(P, names, x, nblocks, pad):
     """x complex64 [B, E, T, Y, X] -> (out complex64, saved)."""
     B, E, T, Y, X = x.shape
-    Tp = T + 2 * pad
-    if Tp % 4 or Y % 4 or X % 4:
-        raise NotImplementedError("dl_cs HIP path: T+2*pad, Y and X must be multiples of 4")
-    grid = (B, Tp, Y, X)
     cin = 2 * E
     F = P[names["init_w"]].shape[0]
-    u = K.swin_pre(x.contiguous(), torch.float32, pad, PAD_CIN)
-    r = [_conv(u, cin, P[names["init_w"]], F, F, grid, bias=P[names["init_b"]], relu_out=1)]
+    u, grid, box = _pre(x, pad)
+    r = [_zero(_conv(u, cin, P[names["init_w"]], F, F, grid, bias=P[names["init_b"]], relu_out=1), F, grid, box)]
     ts = []
     for k in range(nblocks):
         wa, ba, wb, bb = (P[n] for n in names["blocks"][k])
-        t = _conv(r[-1], F, wa, F, F, grid, bias=ba, relu_out=1)
+        t = _zero(_conv(r[-1], F, wa, F, F, grid, bias=ba, relu_out=1), F, grid, box)
         ts.append(t)
-        r.append(_conv(t, F, wb, F, F, grid, bias=bb, res=r[-1], relu_out=1))
+        r.append(_zero(_conv(t, F, wb, F, F, grid, bias=bb, res=r[-1], relu_out=1), F, grid, box))
     o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u,
               out_dtype=torch.float32)
-    out = K.swin_post(o, (B, E, T, Y, X), pad)
-    _capture(r, ts, grid, F)
-    return out, dict(u=u, r=r, ts=ts, grid=grid, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
+    out = _post(o, (B, E, T, Y, X), pad, grid, box)
+    _capture(r, ts, grid, F, box)
+    return out, dict(u=u, r=r, ts=ts, grid=grid, box=box, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
 
 
 def resnet_backward(P, names, sv, gout, grads):
-    grid, cin, F, pad = sv["grid"], sv["cin"], sv["F"], sv["pad"]
+    grid, box, cin, F, pad = sv["grid"], sv["box"], sv["cin"], sv["F"], sv["pad"]
     rows = grid[0] * grid[1] * grid[2] * grid[3]
     r, ts, u = sv["r"], sv["ts"], sv["u"]
-    go = K.swin_post_bwd(gout.contiguous(), torch.float32, pad, PAD_CIN)           # dL/d out (and the + u path)
+    go = _post_bwd(gout, pad, grid, box)                                            # dL/d out (and the + u path)
     # final layer: out = conv_f(r_L) + b_f + u
     _wgrad(r[-1], F, go, cin, grid, grads[names["final_w"]], grads[names["final_b"]], rows)
     g = _dgrad(go, cin, P[names["final_w"]], F, F, grid, mask=r[-1])                # dL/d o_L (through relu)
@@ -110,52 +156,51 @@ def resnet_backward(P, names, sv, gout, grads):
     # init layer: o_0 = conv0(u) + b0 ;  du = conv0^T(g) + go (the final residual)
     _wgrad(u, cin, g, F, grid, grads[names["init_w"]], grads[names["init_b"]], rows)
     du = _dgrad(g, F, P[names["init_w"]], cin, PAD_CIN, grid, res=go, out_dtype=torch.float32)
-    return K.swin_pre_bwd(du, sv["shape"], pad)
+    return _pre_bwd(du, sv["shape"], pad, grid, box)
 
 
 def gated_forward(P, names, x, nblocks, pad, gate):
     """The trunk of the gated families (se3d.SeGate, CBAM.CbamGate), which keep conv_b's
     output o_k un-activated and put a gate between it and the residual:
 
-        r_{k+1}, saved = gate.fwd(o_k, r_k, w, grid, F)        r_{k+1} = relu(gate(o_k) + r_k)
+        r_{k+1}, saved = gate.fwd(o_k, r_k, w, grid, F, N)     r_{k+1} = relu(gate(o_k) + r_k)
 
-    with w the block's gate parameters (names["blocks"][k][4:]) and saved whatever the
+    with w the block's gate parameters (names["blocks"][k][4:]), N the voxels per batch item
+    its means run over (the box's; o_k is zero on slack rows) and saved whatever the
     gate's backward needs besides o_k.  x complex64 [B, E, T, Y, X] -> (out complex64, saved)."""
     B, E, T, Y, X = x.shape
-    Tp = T + 2 * pad
-    if Tp % 4 or Y % 4 or X % 4:
-        raise NotImplementedError("dl_cs HIP path: T+2*pad, Y and X must be multiples of 4")
-    grid = (B, Tp, Y, X)
     cin = 2 * E
     F = P[names["init_w"]].shape[0]
-    u = K.swin_pre(x.contiguous(), torch.float32, pad, PAD_CIN)
-    r = [_conv(u, cin, P[names["init_w"]], F, F, grid, bias=P[names["init_b"]], relu_out=1)]
+    u, grid, box = _pre(x, pad)
+    r = [_zero(_conv(u, cin, P[names["init_w"]], F, F, grid, bias=P[names["init_b"]], relu_out=1), F, grid, box)]
     ts, os_, gs = [], [], []
+    N = _nvox(grid, box)
     for k in range(nblocks):
         wa, ba, wb, bb, *w = (P[n] for n in names["blocks"][k])
-        t = _conv(r[-1], F, wa, F, F, grid, bias=ba, relu_out=1)
-        o = _conv(t, F, wb, F, F, grid, bias=bb)
-        r_next, saved = gate.fwd(o, r[-1], w, grid, F)
+        t = _zero(_conv(r[-1], F, wa, F, F, grid, bias=ba, relu_out=1), F, grid, box)
+        o = _zero(_conv(t, F, wb, F, F, grid, bias=bb), F, grid, box)
+        r_next, saved = gate.fwd(o, r[-1], w, grid, F, N)
         r.append(r_next); ts.append(t); os_.append(o); gs.append(saved)
     o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u,
               out_dtype=torch.float32)
-    out = K.swin_post(o, (B, E, T, Y, X), pad)
-    _capture(r, ts, grid, F)
-    return out, dict(u=u, r=r, ts=ts, os=os_, gs=gs, grid=grid, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
+    out = _post(o, (B, E, T, Y, X), pad, grid, box)
+    _capture(r, ts, grid, F, box)
+    return out, dict(u=u, r=r, ts=ts, os=os_, gs=gs, grid=grid, box=box, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
 
 
 def gated_backward(P, names, sv, gout, grads, gate):
     """Backward of gated_forward.  Per block
 
-        do = gate.bwd(g, r_{k+1}, o_k, saved, w, gw, grid, F)
+        do = gate.bwd(g, r_{k+1}, o_k, saved, w, gw, grid, F, N)
 
     takes g = dL/dr_{k+1}, masks it in place into gz = g [r_{k+1} > 0] (the gradient of the
     ReLU's argument, and so also the residual gradient into r_k), accumulates the gate
     parameters' gradients into gw and returns conv_b's output gradient."""
-    grid, cin, F, pad = sv["grid"], sv["cin"], sv["F"], sv["pad"]
+    grid, box, cin, F, pad = sv["grid"], sv["box"], sv["cin"], sv["F"], sv["pad"]
     rows = grid[0] * grid[1] * grid[2] * grid[3]
+    N = _nvox(grid, box)
     r, ts, u = sv["r"], sv["ts"], sv["u"]
-    go = K.swin_post_bwd(gout.contiguous(), torch.float32, pad, PAD_CIN)           # dL/d out (and the + u path)
+    go = _post_bwd(gout, pad, grid, box)                                            # dL/d out (and the + u path)
     # final layer: out = conv_f(r_L) + b_f + u
     _wgrad(r[-1], F, go, cin, grid, grads[names["final_w"]], grads[names["final_b"]], rows)
     g = _dgrad(go, cin, P[names["final_w"]], F, F, grid)                            # dL/d r_L
@@ -163,7 +208,7 @@ def gated_backward(P, names, sv, gout, grads, gate):
         wa, ba, wb, bb, *w = (P[n] for n in names["blocks"][k])
         gwa, gba, gwb, gbb, *gw = (grads[n] for n in names["blocks"][k])
         # r_{k+1} = relu(gate(o) + r_k), o = conv_b(t_k) + b_b, t_k = relu(conv_a(r_k) + b_a)
-        do = gate.bwd(g, r[k + 1], sv["os"][k], sv["gs"][k], w, gw, grid, F)        # g is now gz
+        do = _zero(gate.bwd(g, r[k + 1], sv["os"][k], sv["gs"][k], w, gw, grid, F, N), F, grid, box)   # g is now gz
         _wgrad(ts[k], F, do, F, grid, gwb, gbb, rows)
         gt = _dgrad(do, F, wb, F, F, grid, mask=ts[k])
         _wgrad(r[k], F, gt, F, grid, gwa, gba, rows)
@@ -172,7 +217,7 @@ def gated_backward(P, names, sv, gout, grads, gate):
     # init layer: o_0 = conv0(u) + b0 ;  du = conv0^T(g) + go (the final residual)
     _wgrad(u, cin, g, F, grid, grads[names["init_w"]], grads[names["init_b"]], rows)
     du = _dgrad(g, F, P[names["init_w"]], cin, PAD_CIN, grid, res=go, out_dtype=torch.float32)
-    return K.swin_pre_bwd(du, sv["shape"], pad)
+    return _pre_bwd(du, sv["shape"], pad, grid, box)
 
 
 class _TrunkFn(torch.autograd.Function):

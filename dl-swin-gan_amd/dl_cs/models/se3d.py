@@ -10,8 +10,9 @@ the dlcs_se_* kernels (se.hip).
 As in resnet3d.py the pre-activation ReLUs are in place (se3d:416-417 build the
 ConvBlocks of resnet3d), so a block's residual adds relu(input) and every block
 output is only ever consumed through a ReLU; the HIP forward stores r = relu(.)
-directly.  With N = Tp Y X voxels per batch item (time pad included), R = rr the
-hidden width (se3d:325 passes rr straight to FC(out_chans, rr)):
+directly.  With N = Tp Y X voxels per batch item (time pad included; on a grid that
+the trunk pads to multiples of 4 still the true grid's count, the added rows hold
+zeros), R = rr the hidden width (se3d:325 passes rr straight to FC(out_chans, rr)):
 
     u   = pre(x)                                cat(re, im), circular T pad
     r0  = relu(conv0(u))
@@ -97,19 +98,27 @@ class SeGate:
     gw their gradients, saved = (m, h, s); the equations are in the module docstring."""
 
     @staticmethod
-    def fwd(o, r_prev, w, grid, F):
-        B, N = grid[0], grid[1] * grid[2] * grid[3]
-        m = K.se_pool(o, B, N, F)
-        h, s = K.se_gate(m, *w)
-        return K.se_scale_res_relu(o, s, r_prev, B, N, F), (m, h, s)
+    def pool(o, grid, F, N):
+        """m [B, F] = the mean of o over a batch item's N voxels; o is zero on the rows of a
+        padded grid that lie outside them, so the mean over all rows is rescaled."""
+        rows = grid[1] * grid[2] * grid[3]
+        m = K.se_pool(o, grid[0], rows, F)
+        return m if rows == N else K.scaled_copy(m, m.dtype, rows / N)
 
     @staticmethod
-    def bwd(g, r_next, o, saved, w, gw, grid, F):
-        B, N = grid[0], grid[1] * grid[2] * grid[3]
+    def fwd(o, r_prev, w, grid, F, N):
+        B, rows = grid[0], grid[1] * grid[2] * grid[3]
+        m = SeGate.pool(o, grid, F, N)
+        h, s = K.se_gate(m, *w)
+        return K.se_scale_res_relu(o, s, r_prev, B, rows, F), (m, h, s)
+
+    @staticmethod
+    def bwd(g, r_next, o, saved, w, gw, grid, F, N):
+        B, rows = grid[0], grid[1] * grid[2] * grid[3]
         (m, h, s), (w1, _, w2, _) = saved, w
-        ds = K.se_bwd_reduce(g, r_next, o, B, N, F)
+        ds = K.se_bwd_reduce(g, r_next, o, B, rows, F)
         dm = K.se_gate_bwd(ds, s, h, m, w1, w2, 1.0 / N, *gw)
-        return K.se_bwd_apply(g, r_next, s, dm, B, N, F)                            # g is now gz
+        return K.se_bwd_apply(g, r_next, s, dm, B, rows, F)                         # g is now gz
 
 
 class SeResNet(_TrunkNet):

@@ -246,7 +246,8 @@ int dlcs_window_attn_bwd(int dtype, const void* qkv, const void* out, const void
 
 /* ---------------------------------------------------------------------------
  * Conv3d(k=3, stride 1, pad 1) -- s3d:120-134 inside ConvBlock s3d:225-270.
- * Activations in the patch-blocked channels-last layout (D, H, W multiples of 4):
+ * Activations in the patch-blocked channels-last layout (D, H, W multiples of 4; any
+ * other grid runs as a box in the grid rounded up, see "A box inside a padded grid"):
  *   row(b,t,y,x) = ((((b*D/4 + t/4)*H/4 + y/4)*W/4 + x/4)*64 + (t%4)*16 + (y%4)*4 + x%4
  * in [rows, cin_ld] (channels >= cin ignored), weights packed by
  * dlcs_conv3d_pack_weights: [27][cout_pad][cin_pad], cin_pad % 32 == 0.
@@ -531,8 +532,39 @@ int dlcs_swin_post(int dtype, const void* o, void* out, int64_t B, int64_t E, in
 int dlcs_swin_post_bwd(int dtype, const void* gout, void* go, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X,
                        int64_t pad, int64_t ldc, dlcs_stream_t stream);
 
+/* ---- A box inside a padded grid (box.hip) --------------------------------------------
+ * What lets the ResNet, SE and CBAM regularisers take any grid.  The conv, SE and CBAM
+ * entry points keep requiring D, H, W multiples of 4; a true grid ("box") (B, D, H, W)
+ * sits at the origin of a padded grid (B, Dp, Hp, Wp), Dp >= D, Hp >= H, Wp >= W
+ * multiples of 4, whose patch-blocked rows those entry points receive.  Rows whose
+ * (t, y, x) lies outside the box are slack rows; a k3 / pad-1 conv on the padded grid is
+ * the zero-padded conv on the box when every tensor a stencil or reduction reads is zero
+ * on them.  fp32.
+ *
+ *   box_pre / _pre_bwd / _post / _post_bwd: dlcs_swin_pre / ... above with D = T + 2 pad,
+ *     H = Y, W = X, rows addressed in (Dp, Hp, Wp); any T, Y, X >= 1.  pre and post_bwd
+ *     write every row of the padded grid, slack rows +0.0 in all ldc columns; pre_bwd and
+ *     post read rows of the box only.  Without slack: the bits of the dlcs_swin_* calls.
+ *   box_zero: +0.0 into columns [0, C) of every slack row of x [B Dp Hp Wp, ld].  Reads
+ *     nothing, writes nothing to rows of the box or to columns [C, ld); work and bytes
+ *     are proportional to the slack rows.  16-B stores when C % 4 == 0, ld % 4 == 0 and
+ *     x is 16-B aligned, else one float at a time.  No slack: no launch, returns 0.
+ *
+ * Padded sizes not multiples of 4, a box larger than the padded grid, or (box_zero)
+ * B > 65535: DLCS_ERR_UNSUPPORTED_SIZE and nothing is written.                         */
+int dlcs_box_pre(const void* x, float* u, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                 int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
+int dlcs_box_pre_bwd(const float* gu, void* gx, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                     int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
+int dlcs_box_post(const float* o, void* out, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                  int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
+int dlcs_box_post_bwd(const void* gout, float* go, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                      int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
+int dlcs_box_zero(float* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_t Hp, int64_t Wp, int64_t D, int64_t H,
+                  int64_t W, dlcs_stream_t stream);
+
 /* Elementwise / layout helpers.
- *   axpby:   y = a x + b y  (dtype conversion allowed; with b == 0 y is not read)
+ *   axpby:  y = a x + b y  (dtype conversion allowed; with b == 0 y is not read)
  *   permute: dst (shape dst_shape, contiguous) [i] (+)= src[sum_k i_k * src_strides[k]], ndim <= 6
  *   fill_bias: out[r, c] = bias[c % period] (or 0)
  *   relu_grad: g[i] = (a[i] > 0) ? g[i] : 0, in place (a = stored post-ReLU activation) */
@@ -635,7 +667,9 @@ int dlcs_rows_add(float* dst, const int32_t* idx, const float* src, int64_t nrow
  * se3d = dl_cs/models/se3d.py: SeBlock :302-348 (GlobalAvgPool :80-97 -> FC -> ReLU ->
  * FC -> sigmoid) and the gated residual of SeResBlock :435-438.  fp32, on the
  * patch-blocked rows [B N, ld] of a conv output with C channels; batch item b is the
- * rows [b N, (b + 1) N), N = Tp Y X voxels (time pad included).  W1 [R, C], b1 [R],
+ * rows [b N, (b + 1) N), N = Tp Y X voxels (time pad included; for a box in a padded
+ * grid N is the padded grid's row count, the caller rescales the pooled mean by
+ * N / (D H W) and passes inv_n = 1 / (D H W)).  W1 [R, C], b1 [R],
  * W2 [C, R], b2 [C] are the two nn.Linear of the block (R = the config's RR, the hidden
  * width).  1 <= C <= 1024, 1 <= R <= 256, B <= 65535 for the row passes: beyond,
  * DLCS_ERR_UNSUPPORTED_SIZE and nothing is written.  Rows are read and written 16 B at a
