@@ -1,5 +1,5 @@
 // A box inside a padded grid: what lets the conv trunks of the ResNet, SE and CBAM
-// regularisers take any grid size.  fp32.
+// regularisers take any grid size.  fp32 rows; the *_bf16 entries write / clear bf16 rows.
 //
 // The conv, SE and CBAM kernels work on the patch-blocked channels-last rows of a grid
 // (B, Dp, Hp, Wp) whose axes are multiples of 4.  A true grid ("box") (B, D, H, W),
@@ -19,7 +19,8 @@
 //       t in [0, D), y in [0, H), x in [W, Wp)        D H (Wp - W) rows
 //   and the kernel enumerates exactly those: one thread per (slack row, column chunk),
 //   4 columns as one 16-B store when C % 4 == 0, ld % 4 == 0 and the base is 16-B
-//   aligned (se.hip's rule), else one float.  It reads no memory.
+//   aligned (se.hip's rule), else one float.  It reads no memory.  bf16 rows: 8 columns per
+//   16-B store when C % 8 == 0, ld % 8 == 0 and the base is aligned, else one element.
 #include "dlcs_common.h"
 
 namespace {
@@ -37,8 +38,8 @@ struct BoxDims {
 
 // u[b, t', y, x, c] = (c < E ? Re : Im) x[b, c mod E, (t' - pad) mod T, y, x] inside the box,
 // c < 2E; zero for c >= 2E and on slack rows.  POST_BWD: no wrap, zero for t' - pad outside [0, T).
-template <bool POST_BWD>
-__global__ void __launch_bounds__(256) box_scatter_kernel(const float2* x, float* u, BoxDims d) {
+template <bool POST_BWD, typename T>
+__global__ void __launch_bounds__(256) box_scatter_kernel(const float2* x, T* u, BoxDims d) {
     const int D = d.Tn + 2 * d.pad;
     const long total = (long)d.B * d.Dp * d.Hp * d.Wp;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -47,7 +48,7 @@ __global__ void __launch_bounds__(256) box_scatter_kernel(const float2* x, float
         const int y = (int)(q % d.Hp); q /= d.Hp;
         const int tp = (int)(q % d.Dp);
         const int b = (int)(q / d.Dp);
-        float* dst = u + box_row(b, tp, y, xx, d.Dp, d.Hp, d.Wp) * d.ldc;
+        T* dst = u + box_row(b, tp, y, xx, d.Dp, d.Hp, d.Wp) * d.ldc;
         bool in = tp < D && y < d.Y && xx < d.X;
         int t = tp - d.pad;
         if (POST_BWD) in = in && t >= 0 && t < d.Tn;
@@ -59,7 +60,7 @@ __global__ void __launch_bounds__(256) box_scatter_kernel(const float2* x, float
                 const float2 z = x[((((long)b * d.E + e) * d.Tn + t) * d.Y + y) * d.X + xx];
                 v = (c < d.E) ? z.x : z.y;
             }
-            dst[c] = v;
+            dst[c] = from_f<T>(v);
         }
     }
 }
@@ -98,8 +99,9 @@ struct ZeroDims {
 };
 
 // blockIdx.y = batch item; grid-stride over (slack row, column chunk) pairs of V columns
-template <int V>
-__global__ void __launch_bounds__(256) box_zero_kernel(float* x, long ld, int nch, ZeroDims z) {
+// (V > 1: one 16-B store, 4 floats or 8 bf16)
+template <typename T, int V>
+__global__ void __launch_bounds__(256) box_zero_kernel(T* x, long ld, int nch, ZeroDims z) {
     const int b = blockIdx.y;
     const long total = (z.n1 + z.n2 + z.n3) * nch;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -123,12 +125,12 @@ __global__ void __launch_bounds__(256) box_zero_kernel(float* x, long ld, int nc
             y = (int)(s % z.H);
             t = (int)(s / z.H);
         }
-        float* dst = x + box_row(b, t, y, xx, z.Dp, z.Hp, z.Wp) * ld + (long)ch * V;
-        if constexpr (V == 4) {
-            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+        T* dst = x + box_row(b, t, y, xx, z.Dp, z.Hp, z.Wp) * ld + (long)ch * V;
+        if constexpr (V > 1) {
+            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};             // 16 B of +0.0 in either format
             *reinterpret_cast<f32x4*>(dst) = v;
         } else {
-            *dst = 0.0f;
+            *dst = from_f<T>(0.0f);
         }
     }
 }
@@ -167,8 +169,17 @@ int dlcs_box_pre(const void* x, float* u, int64_t B, int64_t E, int64_t T, int64
                  int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
     BoxDims d;
     if (const int rc = box_dims(&d, x, u, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
-    hipLaunchKernelGGL(box_scatter_kernel<false>, dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0, (hipStream_t)stream,
-                       (const float2*)x, u, d);
+    hipLaunchKernelGGL((box_scatter_kernel<false, float>), dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0,
+                       (hipStream_t)stream, (const float2*)x, u, d);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_pre_bf16(const void* x, void* u, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                      int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
+    BoxDims d;
+    if (const int rc = box_dims(&d, x, u, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
+    hipLaunchKernelGGL((box_scatter_kernel<false, bf16>), dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0,
+                       (hipStream_t)stream, (const float2*)x, (bf16*)u, d);
     return dlcs_launch_status();
 }
 
@@ -194,8 +205,17 @@ int dlcs_box_post_bwd(const void* gout, float* go, int64_t B, int64_t E, int64_t
                       int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
     BoxDims d;
     if (const int rc = box_dims(&d, gout, go, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
-    hipLaunchKernelGGL(box_scatter_kernel<true>, dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0, (hipStream_t)stream,
-                       (const float2*)gout, go, d);
+    hipLaunchKernelGGL((box_scatter_kernel<true, float>), dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0,
+                       (hipStream_t)stream, (const float2*)gout, go, d);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_post_bwd_bf16(const void* gout, void* go, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X,
+                           int64_t pad, int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream) {
+    BoxDims d;
+    if (const int rc = box_dims(&d, gout, go, B, E, T, Y, X, pad, Dp, Hp, Wp, ldc)) return rc;
+    hipLaunchKernelGGL((box_scatter_kernel<true, bf16>), dim3(box_blocks(B * Dp * Hp * Wp)), dim3(256), 0,
+                       (hipStream_t)stream, (const float2*)gout, (bf16*)go, d);
     return dlcs_launch_status();
 }
 
@@ -210,9 +230,26 @@ int dlcs_box_zero(float* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_
     const int nch = (int)(vec ? C / 4 : C);
     const dim3 grid(box_blocks(n * nch), (unsigned)B);
     if (vec)
-        hipLaunchKernelGGL(box_zero_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
+        hipLaunchKernelGGL((box_zero_kernel<float, 4>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
     else
-        hipLaunchKernelGGL(box_zero_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
+        hipLaunchKernelGGL((box_zero_kernel<float, 1>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_zero_bf16(void* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_t Hp, int64_t Wp, int64_t D,
+                       int64_t H, int64_t W, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(x && B > 0 && C > 0 && ld >= C && D > 0 && H > 0 && W > 0);
+    if (!box_grid_ok(Dp, Hp, Wp, D, H, W) || B > 65535 || C >= (1L << 30)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    ZeroDims z{(int)Dp, (int)Hp, (int)Wp, (int)D, (int)H, (int)W, (Dp - D) * Hp * Wp, D * (Hp - H) * Wp, D * H * (Wp - W)};
+    const long n = z.n1 + z.n2 + z.n3;
+    if (n == 0) return 0;
+    const bool vec = C % 8 == 0 && ld % 8 == 0 && al16(x);
+    const int nch = (int)(vec ? C / 8 : C);
+    const dim3 grid(box_blocks(n * nch), (unsigned)B);
+    if (vec)
+        hipLaunchKernelGGL((box_zero_kernel<bf16, 8>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)x, (long)ld, nch, z);
+    else
+        hipLaunchKernelGGL((box_zero_kernel<bf16, 1>), grid, dim3(256), 0, (hipStream_t)stream, (bf16*)x, (long)ld, nch, z);
     return dlcs_launch_status();
 }
 

@@ -1,5 +1,6 @@
 // Spatial gate of the CBAM-ResNet regulariser (reference CBAM.py:425-521) around the
-// fused ResNet conv trunk and the SE channel gate (se.hip), fp32.  Row operands are the
+// fused ResNet conv trunk and the SE channel gate (se.hip), fp32 (the five row passes
+// also on bf16 rows, their *_bf16 entry points: se_rows.h).  Row operands are the
 // conv node's patch-blocked channels-last rows [B nT nY nX 64, ld] of a [B, D, H, W]
 // grid (D, H, W multiples of 4; row formula in layout.hip); maps are dense [B, D, H, W]:
 //
@@ -65,8 +66,8 @@ DLCS_DEV float cb_group_sum(float v, int L) {
 // the 16-B path, so a 64-channel row is one access per lane and wider rows amortise the
 // lane sum over several, at most 64 on the scalar path): lane j takes the column chunks
 // j, j + L, ...; the gate row sits in LDS; 4 rows in flight per lane.
-template <int V, bool BWD>
-__global__ void __launch_bounds__(256) cbam_rowdot_kernel(const float* o, const float* g, const float* rn,
+template <typename T, int V, bool BWD>
+__global__ void __launch_bounds__(256) cbam_rowdot_kernel(const T* o, const T* g, const T* rn,
                                                           const float* gate, float scale, float* map, CbGrid gd, int C,
                                                           long ld, long rows_per_block, int L) {
     __shared__ __attribute__((aligned(16))) float sg[kSeMaxC];
@@ -119,8 +120,8 @@ __global__ void __launch_bounds__(256) cbam_rowdot_kernel(const float* o, const 
 // ------------------------------------------------------------------ reduction over voxels
 // part[(b G + blockIdx.x) C + c] = sum over this workgroup's rows of
 // (g [r_next > 0] q[v] + da[v] inv_c) o; se_reduce_kernel's layout and order.
-template <int V>
-__global__ void __launch_bounds__(256) cbam_reduce_kernel(const float* o, const float* g, const float* rn, const float* q,
+template <typename T, int V>
+__global__ void __launch_bounds__(256) cbam_reduce_kernel(const T* o, const T* g, const T* rn, const float* q,
                                                           const float* da, float inv_c, CbGrid gd, int C, long ld,
                                                           long rows_per_block, float* part) {
     __shared__ float sm[256 * V];
@@ -186,10 +187,10 @@ __global__ void __launch_bounds__(256) cbam_reduce_kernel(const float* o, const 
 // APPLY_BWD false: out = relu(q[v] gate o + res) (a = o, bsrc = res; out may alias res).
 // APPLY_BWD true : g (= gio) <- g [r_next > 0] in place (a = r_next),
 //                  out = (g q[v] + da[v] inv_c) gate + dmean.
-template <int V, bool APPLY_BWD>
-__global__ void __launch_bounds__(256) cbam_rows_kernel(const float* a, const float* bsrc, float* gio, const float* gate,
+template <typename T, int V, bool APPLY_BWD>
+__global__ void __launch_bounds__(256) cbam_rows_kernel(const T* a, const T* bsrc, T* gio, const float* gate,
                                                         const float* q, const float* da, float inv_c, const float* dmean,
-                                                        float* out, CbGrid gd, int C, long ld, long rows_per_block) {
+                                                        T* out, CbGrid gd, int C, long ld, long rows_per_block) {
     const int nch = C / V;
     const int cpb = nch < 256 ? nch : 256;
     const int ngrp = 256 / cpb;
@@ -468,9 +469,11 @@ size_t cb_wgrad_bytes(long B, long D, long H, long W) {
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int dlcs_cbam_chan_mean(const float* o, const float* gate, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
+// the row entry points on fp32 (T = float) or bf16 rows
+template <typename T>
+int cbam_chan_mean_rows(const T* o, const float* gate, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
                         int64_t ld, float* map, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(o && gate && map && cb_rows_ok(B, D, H, W, C, ld));
     if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
@@ -479,13 +482,107 @@ int dlcs_cbam_chan_mean(const float* o, const float* gate, int64_t B, int64_t D,
     const dim3 grid(q.G, (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
     const float scale = 1.0f / (float)C;
-    if (se_vec(C, ld, {o}))
-        hipLaunchKernelGGL((cbam_rowdot_kernel<4, false>), grid, dim3(256), 0, st, o, nullptr, nullptr, gate, scale, map, gd,
-                           (int)C, (long)ld, q.rpb, cb_row_lanes(C / 4, 16));
+    if (se_vec<T>(C, ld, {o}))
+        hipLaunchKernelGGL((cbam_rowdot_kernel<T, RowVec<T>::v, false>), grid, dim3(256), 0, st, o, nullptr, nullptr, gate,
+                           scale, map, gd, (int)C, (long)ld, q.rpb, cb_row_lanes(C / RowVec<T>::v, 16));
     else
-        hipLaunchKernelGGL((cbam_rowdot_kernel<1, false>), grid, dim3(256), 0, st, o, nullptr, nullptr, gate, scale, map, gd,
-                           (int)C, (long)ld, q.rpb, cb_row_lanes(C, 64));
+        hipLaunchKernelGGL((cbam_rowdot_kernel<T, 1, false>), grid, dim3(256), 0, st, o, nullptr, nullptr, gate, scale,
+                           map, gd, (int)C, (long)ld, q.rpb, cb_row_lanes(C, 64));
     return dlcs_launch_status();
+}
+
+template <typename T>
+int cbam_scale_res_relu_rows(const T* o, const float* gate, const float* q, const T* res, T* out, int64_t B,
+                             int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(o && gate && q && res && out && out != o && cb_rows_ok(B, D, H, W, C, ld));
+    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    const CbGrid gd = cb_grid(D, H, W);
+    const SeGeom geo = se_geom(B, gd.N);
+    const dim3 grid(geo.G, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (se_vec<T>(C, ld, {o, res, out}))
+        hipLaunchKernelGGL((cbam_rows_kernel<T, RowVec<T>::v, false>), grid, dim3(256), 0, st, o, res, nullptr, gate, q,
+                           nullptr, 0.0f, nullptr, out, gd, (int)C, (long)ld, geo.rpb);
+    else
+        hipLaunchKernelGGL((cbam_rows_kernel<T, 1, false>), grid, dim3(256), 0, st, o, res, nullptr, gate, q, nullptr, 0.0f,
+                           nullptr, out, gd, (int)C, (long)ld, geo.rpb);
+    return dlcs_launch_status();
+}
+
+template <typename T>
+int cbam_bwd_rowdot_rows(const T* g, const T* r_next, const T* o, const float* gate, int64_t B, int64_t D,
+                         int64_t H, int64_t W, int64_t C, int64_t ld, float* dq, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(g && r_next && o && gate && dq && cb_rows_ok(B, D, H, W, C, ld));
+    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    const CbGrid gd = cb_grid(D, H, W);
+    const SeGeom geo = se_geom(B, gd.N);
+    const dim3 grid(geo.G, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (se_vec<T>(C, ld, {g, r_next, o}))
+        hipLaunchKernelGGL((cbam_rowdot_kernel<T, RowVec<T>::v, true>), grid, dim3(256), 0, st, o, g, r_next, gate, 1.0f,
+                           dq, gd, (int)C, (long)ld, geo.rpb, cb_row_lanes(C / RowVec<T>::v, 16));
+    else
+        hipLaunchKernelGGL((cbam_rowdot_kernel<T, 1, true>), grid, dim3(256), 0, st, o, g, r_next, gate, 1.0f, dq, gd,
+                           (int)C, (long)ld, geo.rpb, cb_row_lanes(C, 64));
+    return dlcs_launch_status();
+}
+
+template <typename T>
+int cbam_bwd_reduce_rows(const T* g, const T* r_next, const T* o, const float* q, const float* da, int64_t B,
+                         int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, float* dgate, void* workspace,
+                         size_t workspace_bytes, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(g && r_next && o && q && da && dgate && cb_rows_ok(B, D, H, W, C, ld));
+    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    const CbGrid gd = cb_grid(D, H, W);
+    if (!ws_ok(workspace, workspace_bytes, se_partial_bytes(B, gd.N, C))) return DLCS_ERR_WORKSPACE;
+    const SeGeom geo = se_geom(B, gd.N);
+    const dim3 grid(geo.G, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    const float inv_c = 1.0f / (float)C;
+    if (se_vec<T>(C, ld, {g, r_next, o}))
+        hipLaunchKernelGGL((cbam_reduce_kernel<T, RowVec<T>::v>), grid, dim3(256), 0, st, o, g, r_next, q, da, inv_c, gd,
+                           (int)C, (long)ld, geo.rpb, part);
+    else
+        hipLaunchKernelGGL((cbam_reduce_kernel<T, 1>), grid, dim3(256), 0, st, o, g, r_next, q, da, inv_c, gd, (int)C,
+                           (long)ld, geo.rpb, part);
+    hipLaunchKernelGGL(se_partial_sum_kernel, dim3(cdiv(C, kSeSumCols), (unsigned)B), dim3(1024), 0, st, part, (int)geo.G,
+                       (int)C, 1.0f, dgate);
+    return dlcs_launch_status();
+}
+
+template <typename T>
+int cbam_bwd_apply_rows(T* g, const T* r_next, const float* gate, const float* q, const float* da,
+                        const float* dmean, T* dout, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld,
+                        dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(g && r_next && gate && q && da && dmean && dout && dout != g && cb_rows_ok(B, D, H, W, C, ld));
+    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    const CbGrid gd = cb_grid(D, H, W);
+    const SeGeom geo = se_geom(B, gd.N);
+    const dim3 grid(geo.G, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    const float inv_c = 1.0f / (float)C;
+    if (se_vec<T>(C, ld, {g, r_next, dout}))
+        hipLaunchKernelGGL((cbam_rows_kernel<T, RowVec<T>::v, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate, q,
+                           da, inv_c, dmean, dout, gd, (int)C, (long)ld, geo.rpb);
+    else
+        hipLaunchKernelGGL((cbam_rows_kernel<T, 1, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate, q, da, inv_c,
+                           dmean, dout, gd, (int)C, (long)ld, geo.rpb);
+    return dlcs_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int dlcs_cbam_chan_mean(const float* o, const float* gate, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
+                        int64_t ld, float* map, dlcs_stream_t stream) {
+    return cbam_chan_mean_rows<float>(o, gate, B, D, H, W, C, ld, map, stream);
+}
+
+int dlcs_cbam_chan_mean_bf16(const void* o, const float* gate, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
+                             int64_t ld, float* map, dlcs_stream_t stream) {
+    return cbam_chan_mean_rows<bf16>((const bf16*)o, gate, B, D, H, W, C, ld, map, stream);
 }
 
 int dlcs_cbam_stencil5(const float* in, const float* w5, const float* bias, int transposed, float* out, int64_t B,
@@ -525,36 +622,23 @@ int dlcs_cbam_stencil5_wgrad(const float* dq, const float* a, int64_t B, int64_t
 
 int dlcs_cbam_scale_res_relu(const float* o, const float* gate, const float* q, const float* res, float* out, int64_t B,
                              int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(o && gate && q && res && out && out != o && cb_rows_ok(B, D, H, W, C, ld));
-    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    const CbGrid gd = cb_grid(D, H, W);
-    const SeGeom geo = se_geom(B, gd.N);
-    const dim3 grid(geo.G, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    if (se_vec(C, ld, {o, res, out}))
-        hipLaunchKernelGGL((cbam_rows_kernel<4, false>), grid, dim3(256), 0, st, o, res, nullptr, gate, q, nullptr, 0.0f,
-                           nullptr, out, gd, (int)C, (long)ld, geo.rpb);
-    else
-        hipLaunchKernelGGL((cbam_rows_kernel<1, false>), grid, dim3(256), 0, st, o, res, nullptr, gate, q, nullptr, 0.0f,
-                           nullptr, out, gd, (int)C, (long)ld, geo.rpb);
-    return dlcs_launch_status();
+    return cbam_scale_res_relu_rows<float>(o, gate, q, res, out, B, D, H, W, C, ld, stream);
+}
+
+int dlcs_cbam_scale_res_relu_bf16(const void* o, const float* gate, const float* q, const void* res, void* out, int64_t B,
+                                  int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, dlcs_stream_t stream) {
+    return cbam_scale_res_relu_rows<bf16>((const bf16*)o, gate, q, (const bf16*)res, (bf16*)out, B, D, H, W, C, ld, stream);
 }
 
 int dlcs_cbam_bwd_rowdot(const float* g, const float* r_next, const float* o, const float* gate, int64_t B, int64_t D,
                          int64_t H, int64_t W, int64_t C, int64_t ld, float* dq, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(g && r_next && o && gate && dq && cb_rows_ok(B, D, H, W, C, ld));
-    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    const CbGrid gd = cb_grid(D, H, W);
-    const SeGeom geo = se_geom(B, gd.N);
-    const dim3 grid(geo.G, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    if (se_vec(C, ld, {g, r_next, o}))
-        hipLaunchKernelGGL((cbam_rowdot_kernel<4, true>), grid, dim3(256), 0, st, o, g, r_next, gate, 1.0f, dq, gd, (int)C,
-                           (long)ld, geo.rpb, cb_row_lanes(C / 4, 16));
-    else
-        hipLaunchKernelGGL((cbam_rowdot_kernel<1, true>), grid, dim3(256), 0, st, o, g, r_next, gate, 1.0f, dq, gd, (int)C,
-                           (long)ld, geo.rpb, cb_row_lanes(C, 64));
-    return dlcs_launch_status();
+    return cbam_bwd_rowdot_rows<float>(g, r_next, o, gate, B, D, H, W, C, ld, dq, stream);
+}
+
+int dlcs_cbam_bwd_rowdot_bf16(const void* g, const void* r_next, const void* o, const float* gate, int64_t B, int64_t D,
+                              int64_t H, int64_t W, int64_t C, int64_t ld, float* dq, dlcs_stream_t stream) {
+    return cbam_bwd_rowdot_rows<bf16>((const bf16*)g, (const bf16*)r_next, (const bf16*)o, gate, B, D, H, W, C, ld, dq,
+                                      stream);
 }
 
 size_t dlcs_cbam_bwd_reduce_workspace_bytes(int64_t B, int64_t D, int64_t H, int64_t W, int64_t C) {
@@ -564,43 +648,27 @@ size_t dlcs_cbam_bwd_reduce_workspace_bytes(int64_t B, int64_t D, int64_t H, int
 int dlcs_cbam_bwd_reduce(const float* g, const float* r_next, const float* o, const float* q, const float* da, int64_t B,
                          int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, float* dgate, void* workspace,
                          size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(g && r_next && o && q && da && dgate && cb_rows_ok(B, D, H, W, C, ld));
-    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    const CbGrid gd = cb_grid(D, H, W);
-    if (!ws_ok(workspace, workspace_bytes, se_partial_bytes(B, gd.N, C))) return DLCS_ERR_WORKSPACE;
-    const SeGeom geo = se_geom(B, gd.N);
-    const dim3 grid(geo.G, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    float* part = (float*)workspace;
-    const float inv_c = 1.0f / (float)C;
-    if (se_vec(C, ld, {g, r_next, o}))
-        hipLaunchKernelGGL((cbam_reduce_kernel<4>), grid, dim3(256), 0, st, o, g, r_next, q, da, inv_c, gd, (int)C, (long)ld,
-                           geo.rpb, part);
-    else
-        hipLaunchKernelGGL((cbam_reduce_kernel<1>), grid, dim3(256), 0, st, o, g, r_next, q, da, inv_c, gd, (int)C, (long)ld,
-                           geo.rpb, part);
-    hipLaunchKernelGGL(se_partial_sum_kernel, dim3(cdiv(C, kSeSumCols), (unsigned)B), dim3(1024), 0, st, part, (int)geo.G,
-                       (int)C, 1.0f, dgate);
-    return dlcs_launch_status();
+    return cbam_bwd_reduce_rows<float>(g, r_next, o, q, da, B, D, H, W, C, ld, dgate, workspace, workspace_bytes, stream);
+}
+
+int dlcs_cbam_bwd_reduce_bf16(const void* g, const void* r_next, const void* o, const float* q, const float* da, int64_t B,
+                              int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, float* dgate, void* workspace,
+                              size_t workspace_bytes, dlcs_stream_t stream) {
+    return cbam_bwd_reduce_rows<bf16>((const bf16*)g, (const bf16*)r_next, (const bf16*)o, q, da, B, D, H, W, C, ld, dgate,
+                                      workspace, workspace_bytes, stream);
 }
 
 int dlcs_cbam_bwd_apply(float* g, const float* r_next, const float* gate, const float* q, const float* da,
                         const float* dmean, float* dout, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld,
                         dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(g && r_next && gate && q && da && dmean && dout && dout != g && cb_rows_ok(B, D, H, W, C, ld));
-    if (!cb_rows_supported(B, D, H, W, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    const CbGrid gd = cb_grid(D, H, W);
-    const SeGeom geo = se_geom(B, gd.N);
-    const dim3 grid(geo.G, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    const float inv_c = 1.0f / (float)C;
-    if (se_vec(C, ld, {g, r_next, dout}))
-        hipLaunchKernelGGL((cbam_rows_kernel<4, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate, q, da, inv_c, dmean,
-                           dout, gd, (int)C, (long)ld, geo.rpb);
-    else
-        hipLaunchKernelGGL((cbam_rows_kernel<1, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate, q, da, inv_c, dmean,
-                           dout, gd, (int)C, (long)ld, geo.rpb);
-    return dlcs_launch_status();
+    return cbam_bwd_apply_rows<float>(g, r_next, gate, q, da, dmean, dout, B, D, H, W, C, ld, stream);
+}
+
+int dlcs_cbam_bwd_apply_bf16(void* g, const void* r_next, const float* gate, const float* q, const float* da,
+                             const float* dmean, void* dout, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld,
+                             dlcs_stream_t stream) {
+    return cbam_bwd_apply_rows<bf16>((bf16*)g, (const bf16*)r_next, gate, q, da, dmean, (bf16*)dout, B, D, H, W, C, ld,
+                                     stream);
 }
 
 }  // extern "C"

@@ -18,7 +18,8 @@
 //
 // wgrad kernel: dW[tap][co][ci] += sum_v g[v][co] * act(x)[v + off(tap)][ci],
 // one workgroup per (tap, voxel range), one wave per 32-row co tile, operands
-// staged transposed (voxel-contiguous) in LDS, fp32 atomics per workgroup tile.
+// staged transposed (voxel-contiguous) in LDS, fp32 atomics per workgroup tile.  bf16 has its
+// own kernels: 160 x 160 and thin <-> 160 below, every other channel pair conv3d_wgrad_row.inc.
 // This unit: the generic, bf16 and plain fp32 kernels, the weight pack / unpack and (DIAG
 // build) the superseded kernels; the fp32 convs on fp16 matrix cores: conv3d_f16x3.hip.
 #include "conv3d_common.h"
@@ -1504,6 +1505,7 @@ struct ConvV6Args {                                     // the arguments of the 
 #endif
 #include "conv3d_v6.inc"
 #include "conv3d_v7.inc"
+#include "conv3d_wgrad_row.inc"                         // bf16 weight gradient, any channel pair
 
 // ---------------------------------------------------------------- weight packing
 // mode 0 (forward):  P[tap][co][ci] = W[co][ci][tap]
@@ -1721,6 +1723,7 @@ int wgrad_launch<bf16>(const WgradArgs& a, float* ws, hipStream_t st, bool* bias
     if (mt == 5 && nt == 5) hipLaunchKernelGGL((conv3d_wgrad_tr_kernel<5, 5>), grid, block, 0, st, a, nrange, ppr);
     else if (mt == 5 && nt == 1) hipLaunchKernelGGL((conv3d_wgrad_tr_kernel<5, 1>), grid, block, 0, st, a, nrange, ppr);
     else if (mt == 1 && nt == 5) hipLaunchKernelGGL((conv3d_wgrad_tr_kernel<1, 5>), grid, block, 0, st, a, nrange, ppr);
+    else if (!a.relu_in && al16(a.in) && al16(a.g)) return wgrad_row_launch(a, nrange, ppr, st);   // every other pair
     else return DLCS_ERR_UNSUPPORTED_SIZE;
     return dlcs_launch_status();
 }

@@ -1,6 +1,8 @@
 // Squeeze-excitation gate of the SE-ResNet regulariser (reference se3d.py:302-438)
-// around the fused ResNet conv trunk, fp32, on the patch-blocked channels-last rows
-// [B N, ld] (batch item b = rows [b N, (b + 1) N)):
+// around the fused ResNet conv trunk, on the patch-blocked channels-last rows
+// [B N, ld] (batch item b = rows [b N, (b + 1) N)), fp32 or -- the *_bf16 entry points of
+// the four row passes -- bf16 (se_rows.h: widened on load, fp32 arithmetic, one rounding on
+// store; 8 columns per 16-B access instead of 4).  The [B, C] vectors are always fp32:
 //
 // * dlcs_se_pool            mean[b, c] = (1 / N) sum_rows o                (GlobalAvgPool)
 // * dlcs_se_gate            hidden = relu(W1 mean + b1), gate = sigmoid(W2 hidden + b2)
@@ -28,8 +30,8 @@ namespace {
 // part[(b G + blockIdx.x) C + c] = sum over this workgroup's rows of o (MASKED:
 // of g o where r_next > 0; NaN, +-0 and negatives of r_next are dropped by a
 // select, so nothing of a dropped row reaches the sum).
-template <int V, bool MASKED>
-__global__ void __launch_bounds__(256) se_reduce_kernel(const float* o, const float* g, const float* rn, long N, int C,
+template <typename T, int V, bool MASKED>
+__global__ void __launch_bounds__(256) se_reduce_kernel(const T* o, const T* g, const T* rn, long N, int C,
                                                         long ld, long rows_per_block, float* part) {
     __shared__ float sm[256 * V];
     const int nch = C / V;
@@ -95,9 +97,9 @@ __global__ void __launch_bounds__(256) se_reduce_kernel(const float* o, const fl
 // ------------------------------------------------------------------ element-wise passes
 // APPLY_BWD false: out = relu(o gate + res) (a = o, bsrc = res; out may alias res).
 // APPLY_BWD true : g (= gio) <- g [r_next > 0] in place, out = g gate + dmean (a = r_next).
-template <int V, bool APPLY_BWD>
-__global__ void __launch_bounds__(256) se_rows_kernel(const float* a, const float* bsrc, float* gio, const float* gate,
-                                                      const float* dmean, float* out, long N, int C, long ld,
+template <typename T, int V, bool APPLY_BWD>
+__global__ void __launch_bounds__(256) se_rows_kernel(const T* a, const T* bsrc, T* gio, const float* gate,
+                                                      const float* dmean, T* out, long N, int C, long ld,
                                                       long rows_per_block) {
     const int nch = C / V;
     const int cpb = nch < 256 ? nch : 256;
@@ -258,13 +260,11 @@ __global__ void __launch_bounds__(256) se_gate_bwd_params_kernel(const float* dz
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-size_t dlcs_se_pool_workspace_bytes(int64_t B, int64_t N, int64_t C) {
-    return (B > 0 && N > 0 && C > 0) ? se_partial_bytes(B, N, C) : 0;
-}
-
-int dlcs_se_pool(const float* o, int64_t B, int64_t N, int64_t C, int64_t ld, float* mean, void* workspace,
+// the row entry points on fp32 (T = float) or bf16 rows
+template <typename T>
+int se_pool_rows(const T* o, int64_t B, int64_t N, int64_t C, int64_t ld, float* mean, void* workspace,
                  size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(o && mean && se_rows_ok(B, N, C, ld));
     if (!se_rows_supported(B, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
@@ -273,15 +273,88 @@ int dlcs_se_pool(const float* o, int64_t B, int64_t N, int64_t C, int64_t ld, fl
     const SeGeom q = se_geom(B, N);
     float* part = (float*)workspace;
     const dim3 grid(q.G, (unsigned)B);
-    if (se_vec(C, ld, {o}))
-        hipLaunchKernelGGL((se_reduce_kernel<4, false>), grid, dim3(256), 0, st, o, nullptr, nullptr, (long)N, (int)C,
-                           (long)ld, q.rpb, part);
+    if (se_vec<T>(C, ld, {o}))
+        hipLaunchKernelGGL((se_reduce_kernel<T, RowVec<T>::v, false>), grid, dim3(256), 0, st, o, nullptr, nullptr,
+                           (long)N, (int)C, (long)ld, q.rpb, part);
     else
-        hipLaunchKernelGGL((se_reduce_kernel<1, false>), grid, dim3(256), 0, st, o, nullptr, nullptr, (long)N, (int)C,
+        hipLaunchKernelGGL((se_reduce_kernel<T, 1, false>), grid, dim3(256), 0, st, o, nullptr, nullptr, (long)N, (int)C,
                            (long)ld, q.rpb, part);
-    hipLaunchKernelGGL(se_partial_sum_kernel, dim3(cdiv(C, kSeSumCols), (unsigned)B), dim3(1024), 0, st, part, (int)q.G, (int)C,
-                       (float)N, mean);
+    hipLaunchKernelGGL(se_partial_sum_kernel, dim3(cdiv(C, kSeSumCols), (unsigned)B), dim3(1024), 0, st, part, (int)q.G,
+                       (int)C, (float)N, mean);
     return dlcs_launch_status();
+}
+
+template <typename T>
+int se_scale_res_relu_rows(const T* o, const float* gate, const T* res, T* out, int64_t B, int64_t N,
+                           int64_t C, int64_t ld, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(o && gate && res && out && out != o && se_rows_ok(B, N, C, ld));
+    if (!se_rows_supported(B, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    const SeGeom q = se_geom(B, N);
+    const dim3 grid(q.G, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (se_vec<T>(C, ld, {o, res, out}))
+        hipLaunchKernelGGL((se_rows_kernel<T, RowVec<T>::v, false>), grid, dim3(256), 0, st, o, res, nullptr, gate,
+                           nullptr, out, (long)N, (int)C, (long)ld, q.rpb);
+    else
+        hipLaunchKernelGGL((se_rows_kernel<T, 1, false>), grid, dim3(256), 0, st, o, res, nullptr, gate, nullptr, out,
+                           (long)N, (int)C, (long)ld, q.rpb);
+    return dlcs_launch_status();
+}
+
+template <typename T>
+int se_bwd_reduce_rows(const T* g, const T* r_next, const T* o, int64_t B, int64_t N, int64_t C, int64_t ld,
+                       float* dgate, void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(g && r_next && o && dgate && se_rows_ok(B, N, C, ld));
+    if (!se_rows_supported(B, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    if (!ws_ok(workspace, workspace_bytes, se_partial_bytes(B, N, C))) return DLCS_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const SeGeom q = se_geom(B, N);
+    float* part = (float*)workspace;
+    const dim3 grid(q.G, (unsigned)B);
+    if (se_vec<T>(C, ld, {g, r_next, o}))
+        hipLaunchKernelGGL((se_reduce_kernel<T, RowVec<T>::v, true>), grid, dim3(256), 0, st, o, g, r_next, (long)N,
+                           (int)C, (long)ld, q.rpb, part);
+    else
+        hipLaunchKernelGGL((se_reduce_kernel<T, 1, true>), grid, dim3(256), 0, st, o, g, r_next, (long)N, (int)C, (long)ld,
+                           q.rpb, part);
+    hipLaunchKernelGGL(se_partial_sum_kernel, dim3(cdiv(C, kSeSumCols), (unsigned)B), dim3(1024), 0, st, part, (int)q.G,
+                       (int)C, 1.0f, dgate);
+    return dlcs_launch_status();
+}
+
+template <typename T>
+int se_bwd_apply_rows(T* g, const T* r_next, const float* gate, const float* dmean, T* dout, int64_t B,
+                      int64_t N, int64_t C, int64_t ld, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(g && r_next && gate && dmean && dout && dout != g && se_rows_ok(B, N, C, ld));
+    if (!se_rows_supported(B, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
+    const SeGeom q = se_geom(B, N);
+    const dim3 grid(q.G, (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (se_vec<T>(C, ld, {g, r_next, dout}))
+        hipLaunchKernelGGL((se_rows_kernel<T, RowVec<T>::v, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate,
+                           dmean, dout, (long)N, (int)C, (long)ld, q.rpb);
+    else
+        hipLaunchKernelGGL((se_rows_kernel<T, 1, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate, dmean, dout,
+                           (long)N, (int)C, (long)ld, q.rpb);
+    return dlcs_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dlcs_se_pool_workspace_bytes(int64_t B, int64_t N, int64_t C) {
+    return (B > 0 && N > 0 && C > 0) ? se_partial_bytes(B, N, C) : 0;
+}
+
+int dlcs_se_pool(const float* o, int64_t B, int64_t N, int64_t C, int64_t ld, float* mean, void* workspace,
+                 size_t workspace_bytes, dlcs_stream_t stream) {
+    return se_pool_rows<float>(o, B, N, C, ld, mean, workspace, workspace_bytes, stream);
+}
+
+int dlcs_se_pool_bf16(const void* o, int64_t B, int64_t N, int64_t C, int64_t ld, float* mean, void* workspace,
+                      size_t workspace_bytes, dlcs_stream_t stream) {
+    return se_pool_rows<bf16>((const bf16*)o, B, N, C, ld, mean, workspace, workspace_bytes, stream);
 }
 
 int dlcs_se_gate(const float* mean, const float* W1, const float* b1, const float* W2, const float* b2, int64_t B,
@@ -295,18 +368,12 @@ int dlcs_se_gate(const float* mean, const float* W1, const float* b1, const floa
 
 int dlcs_se_scale_res_relu(const float* o, const float* gate, const float* res, float* out, int64_t B, int64_t N,
                            int64_t C, int64_t ld, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(o && gate && res && out && out != o && se_rows_ok(B, N, C, ld));
-    if (!se_rows_supported(B, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    const SeGeom q = se_geom(B, N);
-    const dim3 grid(q.G, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    if (se_vec(C, ld, {o, res, out}))
-        hipLaunchKernelGGL((se_rows_kernel<4, false>), grid, dim3(256), 0, st, o, res, nullptr, gate, nullptr, out,
-                           (long)N, (int)C, (long)ld, q.rpb);
-    else
-        hipLaunchKernelGGL((se_rows_kernel<1, false>), grid, dim3(256), 0, st, o, res, nullptr, gate, nullptr, out,
-                           (long)N, (int)C, (long)ld, q.rpb);
-    return dlcs_launch_status();
+    return se_scale_res_relu_rows<float>(o, gate, res, out, B, N, C, ld, stream);
+}
+
+int dlcs_se_scale_res_relu_bf16(const void* o, const float* gate, const void* res, void* out, int64_t B, int64_t N,
+                                int64_t C, int64_t ld, dlcs_stream_t stream) {
+    return se_scale_res_relu_rows<bf16>((const bf16*)o, gate, (const bf16*)res, (bf16*)out, B, N, C, ld, stream);
 }
 
 size_t dlcs_se_bwd_reduce_workspace_bytes(int64_t B, int64_t N, int64_t C) {
@@ -315,22 +382,13 @@ size_t dlcs_se_bwd_reduce_workspace_bytes(int64_t B, int64_t N, int64_t C) {
 
 int dlcs_se_bwd_reduce(const float* g, const float* r_next, const float* o, int64_t B, int64_t N, int64_t C, int64_t ld,
                        float* dgate, void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(g && r_next && o && dgate && se_rows_ok(B, N, C, ld));
-    if (!se_rows_supported(B, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    if (!ws_ok(workspace, workspace_bytes, se_partial_bytes(B, N, C))) return DLCS_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const SeGeom q = se_geom(B, N);
-    float* part = (float*)workspace;
-    const dim3 grid(q.G, (unsigned)B);
-    if (se_vec(C, ld, {g, r_next, o}))
-        hipLaunchKernelGGL((se_reduce_kernel<4, true>), grid, dim3(256), 0, st, o, g, r_next, (long)N, (int)C, (long)ld,
-                           q.rpb, part);
-    else
-        hipLaunchKernelGGL((se_reduce_kernel<1, true>), grid, dim3(256), 0, st, o, g, r_next, (long)N, (int)C, (long)ld,
-                           q.rpb, part);
-    hipLaunchKernelGGL(se_partial_sum_kernel, dim3(cdiv(C, kSeSumCols), (unsigned)B), dim3(1024), 0, st, part, (int)q.G, (int)C,
-                       1.0f, dgate);
-    return dlcs_launch_status();
+    return se_bwd_reduce_rows<float>(g, r_next, o, B, N, C, ld, dgate, workspace, workspace_bytes, stream);
+}
+
+int dlcs_se_bwd_reduce_bf16(const void* g, const void* r_next, const void* o, int64_t B, int64_t N, int64_t C, int64_t ld,
+                            float* dgate, void* workspace, size_t workspace_bytes, dlcs_stream_t stream) {
+    return se_bwd_reduce_rows<bf16>((const bf16*)g, (const bf16*)r_next, (const bf16*)o, B, N, C, ld, dgate, workspace,
+                                    workspace_bytes, stream);
 }
 
 size_t dlcs_se_gate_bwd_workspace_bytes(int64_t B, int64_t C, int64_t R) {
@@ -357,18 +415,12 @@ int dlcs_se_gate_bwd(const float* dgate, const float* gate, const float* hidden,
 
 int dlcs_se_bwd_apply(float* g, const float* r_next, const float* gate, const float* dmean, float* dout, int64_t B,
                       int64_t N, int64_t C, int64_t ld, dlcs_stream_t stream) {
-    DLCS_CHECK_ARG(g && r_next && gate && dmean && dout && dout != g && se_rows_ok(B, N, C, ld));
-    if (!se_rows_supported(B, C)) return DLCS_ERR_UNSUPPORTED_SIZE;
-    const SeGeom q = se_geom(B, N);
-    const dim3 grid(q.G, (unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-    if (se_vec(C, ld, {g, r_next, dout}))
-        hipLaunchKernelGGL((se_rows_kernel<4, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate, dmean, dout,
-                           (long)N, (int)C, (long)ld, q.rpb);
-    else
-        hipLaunchKernelGGL((se_rows_kernel<1, true>), grid, dim3(256), 0, st, r_next, nullptr, g, gate, dmean, dout,
-                           (long)N, (int)C, (long)ld, q.rpb);
-    return dlcs_launch_status();
+    return se_bwd_apply_rows<float>(g, r_next, gate, dmean, dout, B, N, C, ld, stream);
+}
+
+int dlcs_se_bwd_apply_bf16(void* g, const void* r_next, const float* gate, const float* dmean, void* dout, int64_t B,
+                           int64_t N, int64_t C, int64_t ld, dlcs_stream_t stream) {
+    return se_bwd_apply_rows<bf16>((bf16*)g, (const bf16*)r_next, gate, dmean, (bf16*)dout, B, N, C, ld, stream);
 }
 
 }  // extern "C"

@@ -16,11 +16,21 @@ constexpr long kSeMinRows = 64;      // rows per workgroup at least
 
 template <int V> struct SeVec { float v[V]; };
 
+// rows are touched through se_load / se_store only: fp32 rows 4 columns per 16-B access, bf16
+// rows 8 (RowVec<T>::v), or one element; the values a kernel works on are always fp32
+// (V = 8 on floats: the gate row in LDS beside bf16 rows, two 16-B accesses)
+template <typename T> struct RowVec;
+template <> struct RowVec<float> { static constexpr int v = 4; };
+template <> struct RowVec<bf16> { static constexpr int v = 8; };
+
 template <int V> DLCS_DEV SeVec<V> se_load(const float* p) {
     SeVec<V> r;
-    if constexpr (V == 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        r.v[0] = t[0]; r.v[1] = t[1]; r.v[2] = t[2]; r.v[3] = t[3];
+    if constexpr (V == 4 || V == 8) {
+#pragma unroll
+        for (int h = 0; h < V / 4; ++h) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(p + 4 * h);
+            r.v[4 * h] = t[0]; r.v[4 * h + 1] = t[1]; r.v[4 * h + 2] = t[2]; r.v[4 * h + 3] = t[3];
+        }
     } else {
         r.v[0] = *p;
     }
@@ -32,7 +42,31 @@ template <int V> DLCS_DEV void se_store(float* p, const SeVec<V>& r) {
         t[0] = r.v[0]; t[1] = r.v[1]; t[2] = r.v[2]; t[3] = r.v[3];
         *reinterpret_cast<f32x4*>(p) = t;
     } else {
+        static_assert(V == 1, "fp32 rows: 4 columns or 1");
         *p = r.v[0];
+    }
+}
+template <int V> DLCS_DEV SeVec<V> se_load(const bf16* p) {
+    SeVec<V> r;
+    if constexpr (V == 8) {
+        const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r.v[e] = (float)t[e];
+    } else {
+        static_assert(V == 1, "bf16 rows: 8 columns or 1");
+        r.v[0] = (float)*p;
+    }
+    return r;
+}
+template <int V> DLCS_DEV void se_store(bf16* p, const SeVec<V>& r) {     // one rounding, to nearest even
+    if constexpr (V == 8) {
+        bf16x8 t;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) t[e] = (bf16)r.v[e];
+        *reinterpret_cast<bf16x8*>(p) = t;
+    } else {
+        static_assert(V == 1, "bf16 rows: 8 columns or 1");
+        *p = (bf16)r.v[0];
     }
 }
 
@@ -80,8 +114,9 @@ SeGeom se_geom(long B, long N) {
 size_t se_partial_bytes(long B, long N, long C) { return ws_align((size_t)B * se_geom(B, N).G * (size_t)C * sizeof(float)); }
 bool se_rows_ok(long B, long N, long C, long ld) { return B > 0 && N > 0 && C > 0 && ld >= C; }
 bool se_rows_supported(long B, long C) { return C <= kSeMaxC && B <= 65535; }
+template <typename T = float>
 bool se_vec(long C, long ld, std::initializer_list<const void*> ptrs) {
-    if (C % 4 || ld % 4) return false;
+    if (C % RowVec<T>::v || ld % RowVec<T>::v) return false;
     for (const void* p : ptrs)
         if (!al16(p)) return false;
     return true;

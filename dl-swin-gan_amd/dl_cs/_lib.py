@@ -111,6 +111,9 @@ SIGNATURES = {
     "dlcs_box_post": [_P, _P] + [_I64] * 10 + [_P],
     "dlcs_box_post_bwd": [_P, _P] + [_I64] * 10 + [_P],
     "dlcs_box_zero": [_P] + [_I64] * 9 + [_P],
+    "dlcs_box_pre_bf16": [_P, _P] + [_I64] * 10 + [_P],
+    "dlcs_box_post_bwd_bf16": [_P, _P] + [_I64] * 10 + [_P],
+    "dlcs_box_zero_bf16": [_P] + [_I64] * 9 + [_P],
     "dlcs_axpby": [_INT, _INT, _P, _P, _I64, _F, _F, _P],
     "dlcs_relu_grad": [_INT, _P, _INT, _P, _I64, _P],
     "dlcs_permute": [_INT, _INT, _P, _P, _I64, _P, _P, _INT, _P],
@@ -135,23 +138,32 @@ SIGNATURES = {
     # squeeze-excitation gate of the SE-ResNet (se.hip)
     "dlcs_se_pool_workspace_bytes": [_I64, _I64, _I64],
     "dlcs_se_pool": [_P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
+    "dlcs_se_pool_bf16": [_P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
     "dlcs_se_gate": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P],
     "dlcs_se_scale_res_relu": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "dlcs_se_scale_res_relu_bf16": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "dlcs_se_bwd_reduce_workspace_bytes": [_I64, _I64, _I64],
     "dlcs_se_bwd_reduce": [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
+    "dlcs_se_bwd_reduce_bf16": [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
     "dlcs_se_gate_bwd_workspace_bytes": [_I64, _I64, _I64],
     "dlcs_se_gate_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "dlcs_se_bwd_apply": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "dlcs_se_bwd_apply_bf16": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     # spatial gate of the CBAM-ResNet (cbam.hip)
     "dlcs_cbam_chan_mean": [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
+    "dlcs_cbam_chan_mean_bf16": [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
     "dlcs_cbam_stencil5": [_P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _P],
     "dlcs_cbam_stencil5_wgrad_workspace_bytes": [_I64, _I64, _I64, _I64],
     "dlcs_cbam_stencil5_wgrad": [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _SZ, _P],
     "dlcs_cbam_scale_res_relu": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_cbam_scale_res_relu_bf16": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_cbam_bwd_rowdot": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
+    "dlcs_cbam_bwd_rowdot_bf16": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P],
     "dlcs_cbam_bwd_reduce_workspace_bytes": [_I64, _I64, _I64, _I64, _I64],
     "dlcs_cbam_bwd_reduce": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
+    "dlcs_cbam_bwd_reduce_bf16": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _SZ, _P],
     "dlcs_cbam_bwd_apply": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_cbam_bwd_apply_bf16": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     # locally low-rank block operators of the DSLR family (lowrank.hip)
     "dlcs_lr_extract": [_P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_lr_combine": [_P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _P],

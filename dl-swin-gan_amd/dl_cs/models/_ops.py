@@ -635,13 +635,36 @@ def swin_post_bwd(gout, dtype, pad, ldc):
 
 
 # ---------------------------------------------------------------------------- box in a padded grid
-# fp32; grid = (B, Dp, Hp, Wp) multiples of 4, the box (B, T + 2 pad, Y, X) at its origin; dlcs.h "box.hip"
+# grid = (B, Dp, Hp, Wp) multiples of 4, the box (B, T + 2 pad, Y, X) at its origin; dlcs.h "box.hip".
+# fp32 rows; box_pre / box_post_bwd write bf16 rows with dtype=torch.bfloat16 and box_zero follows its
+# tensor, through the *_bf16 wrappers below (the only callers of the bf16 entry points).
 def pad4(n):
     return (n + 3) // 4 * 4
 
 
-def box_pre(x, pad, ldc, grid):
+def box_pre_bf16(x, pad, ldc, grid):
+    B, E, T, Y, X = x.shape
+    u = empty((grid[0] * grid[1] * grid[2] * grid[3], ldc), torch.bfloat16, x.device)
+    call("dlcs_box_pre_bf16", p(x), p(u), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], ldc, S())
+    return u
+
+
+def box_post_bwd_bf16(gout, pad, ldc, grid):
+    B, E, T, Y, X = gout.shape
+    go = empty((grid[0] * grid[1] * grid[2] * grid[3], ldc), torch.bfloat16, gout.device)
+    call("dlcs_box_post_bwd_bf16", p(gout), p(go), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], ldc, S())
+    return go
+
+
+def box_zero_bf16(x, C, grid, box):
+    call("dlcs_box_zero_bf16", p(x), x.shape[-1], C, *grid, *box[1:], S())
+    return x
+
+
+def box_pre(x, pad, ldc, grid, dtype=torch.float32):
     """swin_pre into the rows of the padded grid; slack rows zero."""
+    if dtype == torch.bfloat16:
+        return box_pre_bf16(x, pad, ldc, grid)
     B, E, T, Y, X = x.shape
     u = empty((grid[0] * grid[1] * grid[2] * grid[3], ldc), torch.float32, x.device)
     call("dlcs_box_pre", p(x), p(u), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], ldc, S())
@@ -662,8 +685,10 @@ def box_post(o, shape, pad, grid):
     return out
 
 
-def box_post_bwd(gout, pad, ldc, grid):
+def box_post_bwd(gout, pad, ldc, grid, dtype=torch.float32):
     """swin_post_bwd into the rows of the padded grid; slack rows zero."""
+    if dtype == torch.bfloat16:
+        return box_post_bwd_bf16(gout, pad, ldc, grid)
     B, E, T, Y, X = gout.shape
     go = empty((grid[0] * grid[1] * grid[2] * grid[3], ldc), torch.float32, gout.device)
     call("dlcs_box_post_bwd", p(gout), p(go), B, E, T, Y, X, pad, grid[1], grid[2], grid[3], ldc, S())
@@ -671,7 +696,9 @@ def box_post_bwd(gout, pad, ldc, grid):
 
 
 def box_zero(x, C, grid, box):
-    """x[slack rows, :C] = +0.0 in place (x fp32 [rows of grid, ld]); box = (B, D, H, W)."""
+    """x[slack rows, :C] = +0.0 in place (x fp32 or bf16 [rows of grid, ld]); box = (B, D, H, W)."""
+    if x.dtype == torch.bfloat16:
+        return box_zero_bf16(x, C, grid, box)
     call("dlcs_box_zero", p(x), x.shape[-1], C, *grid, *box[1:], S())
     return x
 
@@ -684,13 +711,28 @@ def relu_grad(g, a):
 
 
 # ---------------------------------------------------------------------------- squeeze-excitation
-# fp32 rows [B N, ld] (batch item b = rows [b N, (b + 1) N)) with C channels; dlcs.h "se.hip"
+# rows [B N, ld] (batch item b = rows [b N, (b + 1) N)) with C channels; dlcs.h "se.hip".  The row
+# passes follow the dtype of their row tensors: fp32 rows call the entry point itself, bf16 rows go
+# through bf16_rows_call to its *_bf16 sibling (row outputs are allocated in the rows' dtype; the
+# [B, C] vectors, the maps and the workspaces are fp32 either way).
+def bf16_rows_call(name, *args):
+    """The only caller of the gates' bf16-row entry points."""
+    call(name + "_bf16", *args)
+
+
+def _rows_call(rows, name, *args):
+    if rows.dtype == torch.bfloat16:
+        bf16_rows_call(name, *args)
+    else:
+        call(name, *args)
+
+
 def se_pool(o, B, N, C, mean=None):
     """mean [B, C] = the per-(batch item, channel) average of o over its N rows (dlcs_se_pool)."""
     if mean is None:
         mean = empty((B, C), torch.float32, o.device)
     ws, nb = _ws("dlcs_se_pool", o.device, B, N, C)
-    call("dlcs_se_pool", p(o), B, N, C, o.shape[-1], p(mean), p(ws), nb, S())
+    _rows_call(o, "dlcs_se_pool", p(o), B, N, C, o.shape[-1], p(mean), p(ws), nb, S())
     return mean
 
 
@@ -709,9 +751,9 @@ def se_gate(mean, w1, b1, w2, b2, hidden=None, gate=None):
 def se_scale_res_relu(o, gate, res, B, N, C, out=None):
     """out = relu(o gate[b, c] + res) (dlcs_se_scale_res_relu); out may be res, not o."""
     if out is None:
-        out = empty(o.shape, torch.float32, o.device)
-    assert o.shape[-1] == res.shape[-1] == out.shape[-1]
-    call("dlcs_se_scale_res_relu", p(o), p(gate), p(res), p(out), B, N, C, o.shape[-1], S())
+        out = empty(o.shape, o.dtype, o.device)
+    assert o.shape[-1] == res.shape[-1] == out.shape[-1] and o.dtype == res.dtype == out.dtype
+    _rows_call(o, "dlcs_se_scale_res_relu", p(o), p(gate), p(res), p(out), B, N, C, o.shape[-1], S())
     return out
 
 
@@ -719,9 +761,9 @@ def se_bwd_reduce(g, r_next, o, B, N, C, dgate=None):
     """dgate [B, C] = sum over a batch item's rows of g (r_next > 0) o (dlcs_se_bwd_reduce)."""
     if dgate is None:
         dgate = empty((B, C), torch.float32, g.device)
-    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1]
+    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1] and g.dtype == r_next.dtype == o.dtype
     ws, nb = _ws("dlcs_se_bwd_reduce", g.device, B, N, C)
-    call("dlcs_se_bwd_reduce", p(g), p(r_next), p(o), B, N, C, g.shape[-1], p(dgate), p(ws), nb, S())
+    _rows_call(g, "dlcs_se_bwd_reduce", p(g), p(r_next), p(o), B, N, C, g.shape[-1], p(dgate), p(ws), nb, S())
     return dgate
 
 
@@ -741,20 +783,20 @@ def se_gate_bwd(dgate, gate, hidden, mean, w1, w2, inv_n, dw1, db1, dw2, db2, dm
 def se_bwd_apply(g, r_next, gate, dmean, B, N, C, dout=None):
     """g *= (r_next > 0) in place; returns dout = g gate[b, c] + dmean[b, c] (dlcs_se_bwd_apply)."""
     if dout is None:
-        dout = empty(g.shape, torch.float32, g.device)
-    assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1]
-    call("dlcs_se_bwd_apply", p(g), p(r_next), p(gate), p(dmean), p(dout), B, N, C, g.shape[-1], S())
+        dout = empty(g.shape, g.dtype, g.device)
+    assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1] and g.dtype == r_next.dtype == dout.dtype
+    _rows_call(g, "dlcs_se_bwd_apply", p(g), p(r_next), p(gate), p(dmean), p(dout), B, N, C, g.shape[-1], S())
     return dout
 
 
 # ---------------------------------------------------------------------------- CBAM spatial gate
-# fp32 rows [B D H W, ld] (patch-blocked) with C channels, dense maps [B, D, H, W]; dlcs.h "cbam.hip";
+# rows [B D H W, ld] (patch-blocked, fp32 or bf16) with C channels, dense fp32 maps [B, D, H, W]; dlcs.h "cbam.hip";
 # grid = (B, D, H, W)
 def cbam_chan_mean(o, gate, grid, C, out=None):
     """a [B, D, H, W] = the channel mean of gate[b, c] o (dlcs_cbam_chan_mean)."""
     if out is None:
         out = empty(grid, torch.float32, o.device)
-    call("dlcs_cbam_chan_mean", p(o), p(gate), *grid, C, o.shape[-1], p(out), S())
+    _rows_call(o, "dlcs_cbam_chan_mean", p(o), p(gate), *grid, C, o.shape[-1], p(out), S())
     return out
 
 
@@ -776,9 +818,9 @@ def cbam_stencil5_wgrad(dq, a, grid, dw5, db5):
 def cbam_scale_res_relu(o, gate, q, res, grid, C, out=None):
     """out = relu(q[v] gate[b, c] o + res) (dlcs_cbam_scale_res_relu); out may be res, not o."""
     if out is None:
-        out = empty(o.shape, torch.float32, o.device)
-    assert o.shape[-1] == res.shape[-1] == out.shape[-1]
-    call("dlcs_cbam_scale_res_relu", p(o), p(gate), p(q), p(res), p(out), *grid, C, o.shape[-1], S())
+        out = empty(o.shape, o.dtype, o.device)
+    assert o.shape[-1] == res.shape[-1] == out.shape[-1] and o.dtype == res.dtype == out.dtype
+    _rows_call(o, "dlcs_cbam_scale_res_relu", p(o), p(gate), p(q), p(res), p(out), *grid, C, o.shape[-1], S())
     return out
 
 
@@ -786,8 +828,8 @@ def cbam_bwd_rowdot(g, r_next, o, gate, grid, C, dq=None):
     """dq [B, D, H, W] = sum_c g (r_next > 0) gate[b, c] o (dlcs_cbam_bwd_rowdot)."""
     if dq is None:
         dq = empty(grid, torch.float32, g.device)
-    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1]
-    call("dlcs_cbam_bwd_rowdot", p(g), p(r_next), p(o), p(gate), *grid, C, g.shape[-1], p(dq), S())
+    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1] and g.dtype == r_next.dtype == o.dtype
+    _rows_call(g, "dlcs_cbam_bwd_rowdot", p(g), p(r_next), p(o), p(gate), *grid, C, g.shape[-1], p(dq), S())
     return dq
 
 
@@ -795,18 +837,18 @@ def cbam_bwd_reduce(g, r_next, o, q, da, grid, C, dgate=None):
     """dgate [B, C] = sum over a batch item's voxels of (g (r_next > 0) q + da / C) o (dlcs_cbam_bwd_reduce)."""
     if dgate is None:
         dgate = empty((grid[0], C), torch.float32, g.device)
-    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1]
+    assert g.shape[-1] == r_next.shape[-1] == o.shape[-1] and g.dtype == r_next.dtype == o.dtype
     ws, nb = _ws("dlcs_cbam_bwd_reduce", g.device, *grid, C)
-    call("dlcs_cbam_bwd_reduce", p(g), p(r_next), p(o), p(q), p(da), *grid, C, g.shape[-1], p(dgate), p(ws), nb, S())
+    _rows_call(g, "dlcs_cbam_bwd_reduce", p(g), p(r_next), p(o), p(q), p(da), *grid, C, g.shape[-1], p(dgate), p(ws), nb, S())
     return dgate
 
 
 def cbam_bwd_apply(g, r_next, gate, q, da, dmean, grid, C, dout=None):
     """g *= (r_next > 0) in place; returns dout = (g q + da / C) gate[b, c] + dmean[b, c] (dlcs_cbam_bwd_apply)."""
     if dout is None:
-        dout = empty(g.shape, torch.float32, g.device)
-    assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1]
-    call("dlcs_cbam_bwd_apply", p(g), p(r_next), p(gate), p(q), p(da), p(dmean), p(dout), *grid, C, g.shape[-1], S())
+        dout = empty(g.shape, g.dtype, g.device)
+    assert g.shape[-1] == r_next.shape[-1] == dout.shape[-1] and g.dtype == r_next.dtype == dout.dtype
+    _rows_call(g, "dlcs_cbam_bwd_apply", p(g), p(r_next), p(gate), p(q), p(da), p(dmean), p(dout), *grid, C, g.shape[-1], S())
     return dout
 
 

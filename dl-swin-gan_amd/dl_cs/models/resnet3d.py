@@ -19,6 +19,12 @@ the HIP forward stores r = relu(o) straight from the producing conv's epilogue:
     r_{k+1} = relu(conv_b(t) + r_k)      ResBlock (r3d:232-240) + next block's ReLU
     out = conv_f(r_L) + u                final_layer + input (r3d:308)
     x'  = post(out)                      crop, complex (r3d:284-294)
+
+Compute dtype bf16 (swin3D.set_compute_dtype): u, r, t (the gated trunks' o too) and every
+F-channel gradient are stored in bf16; the convs accumulate in fp32, add bias and residual in
+fp32 and round once.  Weights, biases and their gradients, the final conv's output, the init
+dgrad's output and the complex boundary stay fp32, and so do the two residuals that cross the
+boundary (the + u of the output and its backward + go: a second, fp32 pre / post_bwd).
 """
 import torch
 from torch import nn
@@ -51,9 +57,15 @@ def _dgrad(g, cout_w, w, cin_w, out_ld, grid, **kw):
     return K.conv3d(g, cout_w, K.conv_pack(w, g.dtype, 1), cin_w, out_ld, grid, **kw)
 
 
+WGRAD_VOX_BF16 = 8192      # voxels per workgroup range of the bf16 tap-row weight gradient
+
+
 def _wgrad(x, cin, g, cout, grid, gw, gb, rows):
     dwp = torch.zeros((27, K.pad32(cout), K.pad32(cin)), dtype=torch.float32, device=x.device)
-    K.conv3d_wgrad(x, cin, 0, g, cout, grid, dwp)
+    if x.dtype == torch.bfloat16:
+        K.conv3d_wgrad(x, cin, 0, g, cout, grid, dwp, vox_per_block=WGRAD_VOX_BF16)
+    else:
+        K.conv3d_wgrad(x, cin, 0, g, cout, grid, dwp)
     K.conv_unpack_grad(dwp, gw, cout, cin)
     K.colsum(g, gb, rows=rows, C=cout, ld=g.shape[-1])
 
@@ -81,24 +93,28 @@ def _capture(r, ts, grid, F, box):
 # rows, which _zero clears: r0, t, r_{k+1} (plain trunk) or conv_b's output o (gated trunk)
 # in the forward, the gate backward's dout in the backward.  Without slack box is None and
 # the launches are the unpadded ones.
-def _pre(x, pad):
-    """x complex64 [B, E, T, Y, X] -> (u, grid, box): grid the (padded) grid of u's rows."""
+def _pre(x, pad, dtype=torch.float32):
+    """x complex64 [B, E, T, Y, X] -> (u, grid, box): grid the (padded) grid of u's rows (of dtype)."""
     B, E, T, Y, X = x.shape
     box = (B, T + 2 * pad, Y, X)
     grid = (B,) + tuple(K.pad4(n) for n in box[1:])
     if grid == box:
-        return K.swin_pre(x.contiguous(), torch.float32, pad, PAD_CIN), grid, None
-    return K.box_pre(x.contiguous(), pad, PAD_CIN, grid), grid, box
+        return K.swin_pre(x.contiguous(), dtype, pad, PAD_CIN), grid, None
+    if dtype == torch.float32:
+        return K.box_pre(x.contiguous(), pad, PAD_CIN, grid), grid, box
+    return K.box_pre(x.contiguous(), pad, PAD_CIN, grid, dtype=dtype), grid, box
 
 
 def _post(o, shape, pad, grid, box):
     return K.swin_post(o, shape, pad) if box is None else K.box_post(o, shape, pad, grid)
 
 
-def _post_bwd(gout, pad, grid, box):
+def _post_bwd(gout, pad, grid, box, dtype=torch.float32):
     if box is None:
-        return K.swin_post_bwd(gout.contiguous(), torch.float32, pad, PAD_CIN)
-    return K.box_post_bwd(gout.contiguous(), pad, PAD_CIN, grid)
+        return K.swin_post_bwd(gout.contiguous(), dtype, pad, PAD_CIN)
+    if dtype == torch.float32:
+        return K.box_post_bwd(gout.contiguous(), pad, PAD_CIN, grid)
+    return K.box_post_bwd(gout.contiguous(), pad, PAD_CIN, grid, dtype=dtype)
 
 
 def _pre_bwd(du, shape, pad, grid, box):
@@ -116,12 +132,14 @@ def _nvox(grid, box):
     return g[1] * g[2] * g[3]
 
 
-def resnet_forward(P, names, x, nblocks, pad):
-    """x complex64 [B, E, T, Y, X] -> (out complex64, saved)."""
+def resnet_forward(P, names, x, nblocks, pad, dtype=torch.float32):
+    """x complex64 [B, E, T, Y, X] -> (out complex64, saved).  dtype: the storage of u and of every
+    F-channel activation (the convs follow their input; the final conv's output stays fp32)."""
     B, E, T, Y, X = x.shape
     cin = 2 * E
     F = P[names["init_w"]].shape[0]
-    u, grid, box = _pre(x, pad)
+    u, grid, box = _pre(x, pad, dtype)
+    u_res = u if dtype == torch.float32 else _pre(x, pad)[0]     # the input residual is added unrounded
     r = [_zero(_conv(u, cin, P[names["init_w"]], F, F, grid, bias=P[names["init_b"]], relu_out=1), F, grid, box)]
     ts = []
     for k in range(nblocks):
@@ -129,18 +147,19 @@ def resnet_forward(P, names, x, nblocks, pad):
         t = _zero(_conv(r[-1], F, wa, F, F, grid, bias=ba, relu_out=1), F, grid, box)
         ts.append(t)
         r.append(_zero(_conv(t, F, wb, F, F, grid, bias=bb, res=r[-1], relu_out=1), F, grid, box))
-    o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u,
+    o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u_res,
               out_dtype=torch.float32)
     out = _post(o, (B, E, T, Y, X), pad, grid, box)
     _capture(r, ts, grid, F, box)
-    return out, dict(u=u, r=r, ts=ts, grid=grid, box=box, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
+    return out, dict(u=u, r=r, ts=ts, grid=grid, box=box, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad, dtype=dtype)
 
 
 def resnet_backward(P, names, sv, gout, grads):
     grid, box, cin, F, pad = sv["grid"], sv["box"], sv["cin"], sv["F"], sv["pad"]
     rows = grid[0] * grid[1] * grid[2] * grid[3]
     r, ts, u = sv["r"], sv["ts"], sv["u"]
-    go = _post_bwd(gout, pad, grid, box)                                            # dL/d out (and the + u path)
+    go = _post_bwd(gout, pad, grid, box, sv["dtype"])                               # dL/d out (and the + u path)
+    go_res = go if sv["dtype"] == torch.float32 else _post_bwd(gout, pad, grid, box)   # the + u path, unrounded
     # final layer: out = conv_f(r_L) + b_f + u
     _wgrad(r[-1], F, go, cin, grid, grads[names["final_w"]], grads[names["final_b"]], rows)
     g = _dgrad(go, cin, P[names["final_w"]], F, F, grid, mask=r[-1])                # dL/d o_L (through relu)
@@ -155,11 +174,11 @@ def resnet_backward(P, names, sv, gout, grads):
         g = K.relu_grad(gr, r[k])                                                  # dL/d o_k
     # init layer: o_0 = conv0(u) + b0 ;  du = conv0^T(g) + go (the final residual)
     _wgrad(u, cin, g, F, grid, grads[names["init_w"]], grads[names["init_b"]], rows)
-    du = _dgrad(g, F, P[names["init_w"]], cin, PAD_CIN, grid, res=go, out_dtype=torch.float32)
+    du = _dgrad(g, F, P[names["init_w"]], cin, PAD_CIN, grid, res=go_res, out_dtype=torch.float32)
     return _pre_bwd(du, sv["shape"], pad, grid, box)
 
 
-def gated_forward(P, names, x, nblocks, pad, gate):
+def gated_forward(P, names, x, nblocks, pad, gate, dtype=torch.float32):
     """The trunk of the gated families (se3d.SeGate, CBAM.CbamGate), which keep conv_b's
     output o_k un-activated and put a gate between it and the residual:
 
@@ -171,7 +190,8 @@ def gated_forward(P, names, x, nblocks, pad, gate):
     B, E, T, Y, X = x.shape
     cin = 2 * E
     F = P[names["init_w"]].shape[0]
-    u, grid, box = _pre(x, pad)
+    u, grid, box = _pre(x, pad, dtype)
+    u_res = u if dtype == torch.float32 else _pre(x, pad)[0]     # the input residual is added unrounded
     r = [_zero(_conv(u, cin, P[names["init_w"]], F, F, grid, bias=P[names["init_b"]], relu_out=1), F, grid, box)]
     ts, os_, gs = [], [], []
     N = _nvox(grid, box)
@@ -181,11 +201,12 @@ def gated_forward(P, names, x, nblocks, pad, gate):
         o = _zero(_conv(t, F, wb, F, F, grid, bias=bb), F, grid, box)
         r_next, saved = gate.fwd(o, r[-1], w, grid, F, N)
         r.append(r_next); ts.append(t); os_.append(o); gs.append(saved)
-    o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u,
+    o = _conv(r[-1], F, P[names["final_w"]], cin, PAD_CIN, grid, bias=P[names["final_b"]], res=u_res,
               out_dtype=torch.float32)
     out = _post(o, (B, E, T, Y, X), pad, grid, box)
     _capture(r, ts, grid, F, box)
-    return out, dict(u=u, r=r, ts=ts, os=os_, gs=gs, grid=grid, box=box, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad)
+    return out, dict(u=u, r=r, ts=ts, os=os_, gs=gs, grid=grid, box=box, cin=cin, F=F, shape=(B, E, T, Y, X), pad=pad,
+                     dtype=dtype)
 
 
 def gated_backward(P, names, sv, gout, grads, gate):
@@ -200,7 +221,8 @@ def gated_backward(P, names, sv, gout, grads, gate):
     rows = grid[0] * grid[1] * grid[2] * grid[3]
     N = _nvox(grid, box)
     r, ts, u = sv["r"], sv["ts"], sv["u"]
-    go = _post_bwd(gout, pad, grid, box)                                            # dL/d out (and the + u path)
+    go = _post_bwd(gout, pad, grid, box, sv["dtype"])                               # dL/d out (and the + u path)
+    go_res = go if sv["dtype"] == torch.float32 else _post_bwd(gout, pad, grid, box)   # the + u path, unrounded
     # final layer: out = conv_f(r_L) + b_f + u
     _wgrad(r[-1], F, go, cin, grid, grads[names["final_w"]], grads[names["final_b"]], rows)
     g = _dgrad(go, cin, P[names["final_w"]], F, F, grid)                            # dL/d r_L
@@ -216,7 +238,7 @@ def gated_backward(P, names, sv, gout, grads, gate):
     g = K.relu_grad(g, r[0])                                                        # dL/d o_0
     # init layer: o_0 = conv0(u) + b0 ;  du = conv0^T(g) + go (the final residual)
     _wgrad(u, cin, g, F, grid, grads[names["init_w"]], grads[names["init_b"]], rows)
-    du = _dgrad(g, F, P[names["init_w"]], cin, PAD_CIN, grid, res=go, out_dtype=torch.float32)
+    du = _dgrad(g, F, P[names["init_w"]], cin, PAD_CIN, grid, res=go_res, out_dtype=torch.float32)
     return _pre_bwd(du, sv["shape"], pad, grid, box)
 
 
@@ -226,7 +248,8 @@ class _TrunkFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, meta, *plist):
         P = dict(zip(meta["order"], plist))
-        out, sv = meta["trunk"][0](P, meta["names"], x.to(torch.complex64), meta["nblocks"], meta["pad"])
+        out, sv = meta["trunk"][0](P, meta["names"], x.to(torch.complex64), meta["nblocks"], meta["pad"],
+                                   dtype=meta["dtype"])
         ctx.state = (P, sv, meta)
         return out
 
@@ -254,6 +277,7 @@ class _TrunkNet(nn.Module):
     BLOCK = None       # block class
     BLOCKS = None      # attribute (and state_dict prefix) of the block list
     TRUNK = None       # (forward, backward) for _TrunkFn
+    DTYPES = (torch.float32, torch.bfloat16)     # compute dtypes (swin3D.get_compute_dtype) the family runs in
 
     def __init__(self, num_resblocks, in_chans, chans, kernel_size, act_type, use_complex_layers, circular_pad,
                  rr=None):
@@ -280,8 +304,11 @@ class _TrunkNet(nn.Module):
         return _wb(f"{pre}.layers.2.conv")
 
     def forward(self, input):
-        if get_compute_dtype() != torch.float32:
-            raise NotImplementedError(f"dl_cs HIP {self.NAME}: fp32 (the generic conv kernels; no bf16 wgrad at 64 ch)")
+        dtype = get_compute_dtype()
+        if dtype not in self.DTYPES:
+            raise NotImplementedError(f"dl_cs HIP {self.NAME}: compute dtype " +
+                                      " or ".join(str(d).replace("torch.", "") for d in self.DTYPES) +
+                                      f" (got {dtype}; bf16 stores the activations, weights and gradients stay fp32)")
         if not input.is_cuda:
             raise RuntimeError(f"dl_cs HIP {self.NAME} needs GPU tensors (no CPU fallback in the product path)")
         params = dict(self.named_parameters())
@@ -290,7 +317,7 @@ class _TrunkNet(nn.Module):
         (iw, ib), (fw, fb) = self.c("init_layer"), self.c("final_layer")
         names = dict(init_w=iw, init_b=ib, final_w=fw, final_b=fb,
                      blocks=[self._block_keys(f"{self.BLOCKS}.{k}") for k in range(nblocks)])
-        meta = dict(order=order, names=names, nblocks=nblocks, pad=self.pad_size, trunk=self.TRUNK)
+        meta = dict(order=order, names=names, nblocks=nblocks, pad=self.pad_size, trunk=self.TRUNK, dtype=dtype)
         return _TrunkFn.apply(input, meta, *[params[n] for n in order])
 
 

@@ -269,6 +269,13 @@ int dlcs_conv3d_k3(int dtype, const void* in, int64_t cin, int64_t cin_ld, const
  * (s3d:120-134) -- in the bf16 SFE weight gradient (thin input side) from the g
  * tiles it already holds (an all-ones MFMA operand, per-range partials summed in
  * a fixed order), otherwise by a column-sum launch after the weight gradient. */
+/* bf16 channel pairs: cout_pad in {32, 64, 96, 128, 160} x cin_pad in {32, 64, 128, 160}, any
+ * cin <= cin_pad, cout <= cout_pad (thin ends in rows of ld 8 included).  160 x 160 and thin <-> 160
+ * have their own kernels; every other pair runs the tap-row kernel (conv3d_wgrad_row.inc), which
+ * takes relu_in = 0 only (relu_in = 1 there: DLCS_ERR_UNSUPPORTED_SIZE; the conv trunks pass 0) and
+ * 16-B aligned in / gout.  It has no workspace and flushes its per-(voxel range, tap row) tiles with
+ * fp32 atomics, as the fp32 generic kernel does: dw_packed is not bit-repeatable from run to run.
+ * vox_per_block sets the voxel range of a workgroup there (<= 0: 16384). */
 /* workspace: bf16 160 x 160: one dW partial slab per voxel range; bf16 thin input with dbias: one row of
  * column sums per range; 0 for every other path (all of fp32). */
 size_t dlcs_conv3d_k3_wgrad_workspace_bytes(int dtype, int64_t cin, int64_t cin_pad, int64_t cout, int64_t cout_pad,
@@ -539,7 +546,9 @@ int dlcs_swin_post_bwd(int dtype, const void* gout, void* go, int64_t B, int64_t
  * multiples of 4, whose patch-blocked rows those entry points receive.  Rows whose
  * (t, y, x) lies outside the box are slack rows; a k3 / pad-1 conv on the padded grid is
  * the zero-padded conv on the box when every tensor a stencil or reduction reads is zero
- * on them.  fp32.
+ * on them.  fp32; box_pre_bf16, box_post_bwd_bf16 and box_zero_bf16 are the same calls on
+ * bf16 rows (u / go written rounded to bf16; box_zero_bf16: 16-B stores of 8 columns when
+ * C % 8 == 0, ld % 8 == 0 and x is 16-B aligned, else one element at a time).
  *
  *   box_pre / _pre_bwd / _post / _post_bwd: dlcs_swin_pre / ... above with D = T + 2 pad,
  *     H = Y, W = X, rows addressed in (Dp, Hp, Wp); any T, Y, X >= 1.  pre and post_bwd
@@ -562,6 +571,12 @@ int dlcs_box_post_bwd(const void* gout, float* go, int64_t B, int64_t E, int64_t
                       int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
 int dlcs_box_zero(float* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_t Hp, int64_t Wp, int64_t D, int64_t H,
                   int64_t W, dlcs_stream_t stream);
+int dlcs_box_pre_bf16(const void* x, void* u, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
+                      int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
+int dlcs_box_post_bwd_bf16(const void* gout, void* go, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X,
+                           int64_t pad, int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
+int dlcs_box_zero_bf16(void* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_t Hp, int64_t Wp, int64_t D,
+                       int64_t H, int64_t W, dlcs_stream_t stream);
 
 /* Elementwise / layout helpers.
  *   axpby:  y = a x + b y  (dtype conversion allowed; with b == 0 y is not read)
@@ -708,6 +723,20 @@ int dlcs_se_gate_bwd(const float* dgate, const float* gate, const float* hidden,
 int dlcs_se_bwd_apply(float* g, const float* r_next, const float* gate, const float* dmean, float* dout, int64_t B,
                       int64_t N, int64_t C, int64_t ld, dlcs_stream_t stream);
 
+/* The same row passes on bf16 rows (o, res, out, g, r_next, dout bf16; mean, gate, dgate, dmean and
+ * the workspaces fp32, sized by the queries above): values are widened on load, the arithmetic and
+ * the fixed-order sums are those of the fp32 entries, and a row output is rounded once on store.
+ * Rows are accessed 16 B (8 columns) at a time when C % 8 == 0, ld % 8 == 0 and the row pointers
+ * are 16-B aligned, else one element at a time. */
+int dlcs_se_pool_bf16(const void* o, int64_t B, int64_t N, int64_t C, int64_t ld, float* mean, void* workspace,
+                      size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_se_scale_res_relu_bf16(const void* o, const float* gate, const void* res, void* out, int64_t B, int64_t N,
+                                int64_t C, int64_t ld, dlcs_stream_t stream);
+int dlcs_se_bwd_reduce_bf16(const void* g, const void* r_next, const void* o, int64_t B, int64_t N, int64_t C,
+                            int64_t ld, float* dgate, void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_se_bwd_apply_bf16(void* g, const void* r_next, const float* gate, const float* dmean, void* dout, int64_t B,
+                           int64_t N, int64_t C, int64_t ld, dlcs_stream_t stream);
+
 /* ---- Spatial gate of the CBAM-ResNet (cbam.hip) -------------------------------------
  * CBAM = dl_cs/models/CBAM.py: SABlock :425-475 (mean over channels -> Conv3d(1, 1, 5,
  * padding 2), no sigmoid) applied to the channel-gated conv output of CBAMResBlock
@@ -755,6 +784,21 @@ int dlcs_cbam_bwd_reduce(const float* g, const float* r_next, const float* o, co
 int dlcs_cbam_bwd_apply(float* g, const float* r_next, const float* gate, const float* q, const float* da,
                         const float* dmean, float* dout, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld,
                         dlcs_stream_t stream);
+
+/* The five row passes on bf16 rows (the rule of the dlcs_se_*_bf16 entries; maps stay fp32). */
+int dlcs_cbam_chan_mean_bf16(const void* o, const float* gate, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
+                             int64_t ld, float* map, dlcs_stream_t stream);
+int dlcs_cbam_scale_res_relu_bf16(const void* o, const float* gate, const float* q, const void* res, void* out,
+                                  int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld,
+                                  dlcs_stream_t stream);
+int dlcs_cbam_bwd_rowdot_bf16(const void* g, const void* r_next, const void* o, const float* gate, int64_t B, int64_t D,
+                              int64_t H, int64_t W, int64_t C, int64_t ld, float* dq, dlcs_stream_t stream);
+int dlcs_cbam_bwd_reduce_bf16(const void* g, const void* r_next, const void* o, const float* q, const float* da,
+                              int64_t B, int64_t D, int64_t H, int64_t W, int64_t C, int64_t ld, float* dgate,
+                              void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_cbam_bwd_apply_bf16(void* g, const void* r_next, const float* gate, const float* q, const float* da,
+                             const float* dmean, void* dout, int64_t B, int64_t D, int64_t H, int64_t W, int64_t C,
+                             int64_t ld, dlcs_stream_t stream);
 
 /* ---- Locally low-rank block operators of the DSLR family (lowrank.hip) ---------------
  * lowrank = dl_cs/mri/lowrank.py: ArrayToBlocks :13-187, Decompose.compose :247-253.
