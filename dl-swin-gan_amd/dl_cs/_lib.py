@@ -170,6 +170,13 @@ SIGNATURES = {
     "dlcs_lr_compose": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_lr_project_l": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_lr_project_r": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    # plane conv of the DSLR family's bf16 path (conv2d.hip)
+    "dlcs_conv2d_k3": [_P, _I64, _I64, _P, _I64, _P, _P, _INT, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _P, _I64,
+                       _P, _INT, _I64, _F, _INT, _P],
+    "dlcs_conv2d_pack_weights": [_P, _P, _I64, _I64, _I64, _I64, _INT, _INT, _P],
+    "dlcs_conv2d_k3_wgrad_workspace_bytes": [_I64, _I64, _I64, _I64, _I64, _INT, _I64],
+    "dlcs_conv2d_k3_wgrad": [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _INT, _I64, _P, _SZ, _P],
+    "dlcs_conv2d_unpack_wgrad": [_P, _P, _I64, _I64, _I64, _I64, _INT, _INT, _P],
 }
 # DIAG build only (libdlcs_hip_diag.so: the superseded bf16 3-plane conv and NT GEMM);
 # bound when the loaded library has them

@@ -940,3 +940,55 @@ def lr_project_r(image, L, weights, win, b, divide=False):
     out = empty((N, T, r), torch.complex64, image.device)
     call("dlcs_lr_project_r", p(image), p(L), p(weights), p(win), int(divide), p(out), E, T, Y, X, b, r, S())
     return out
+
+
+# ---------------------------------------------------------------------------- plane conv (conv2d.hip)
+# bf16 rows [N H W, ld], row = (n H + h) W + w; planes = (N, H, W, KH): KH 3 = N planes of H x W,
+# KH 1 = N H sequences of length W (dlcs.h "Plane conv").
+def _call2d(name, *args):
+    """call(), with the entry's "unsupported size" status as NotImplementedError."""
+    status = getattr(_lib.lib(), name)(*args)
+    if status == 100002:
+        raise NotImplementedError(f"dl_cs HIP plane conv ({name}): KH 3 takes planes up to 16 x 16, KH 1 sequences up "
+                                  "to 256, 1 to 256 channels, fewer than 2^31 pixels and at most 65535 pixel ranges")
+    _lib.check(status, name)
+
+
+def conv2d_pack(w, mode):
+    """torch weight [cout, cin, 3, 3] or [cout, cin, 3] fp32 -> packed bf16 (mode 0 fwd, mode 1 dgrad)."""
+    cout, cin, KH = w.shape[0], w.shape[1], (3 if w.dim() == 4 else 1)
+    rows, cols = (pad32(cout), pad32(cin)) if mode == 0 else (pad32(cin), pad32(cout))
+    out = empty((KH * 3, rows, cols), torch.bfloat16, w.device)
+    _call2d("dlcs_conv2d_pack_weights", p(w.contiguous()), p(out), cout, cin, rows, cols, KH, mode, S())
+    return out
+
+
+def conv2d(x, cin, packed, cout, out_ld, planes, bias=None, out=None, out_dtype=None, mask=None, res=None,
+           res_scale=1.0, relu_out=0):
+    """out[rows, out_ld] = conv2d_k3(x) (+ epilogue) over independent planes; x, mask bf16."""
+    N, H, W, KH = planes
+    if out is None:
+        out = empty((N * H * W, out_ld), out_dtype or x.dtype, x.device)
+    _call2d("dlcs_conv2d_k3", p(x), cin, x.shape[-1], p(packed), packed.shape[2], p(bias), p(out), code(out), cout,
+            packed.shape[1], out.shape[-1], N, H, W, KH, p(mask), mask.shape[-1] if mask is not None else 0, p(res),
+            code(res) if res is not None else F32, res.shape[-1] if res is not None else 0, float(res_scale),
+            int(relu_out), S())
+    return out
+
+
+def conv2d_wgrad(x, cin, g, cout, planes, dw_packed, pix_per_block=4096, dbias=None):
+    """dw_packed fp32 [KH 3, cout_pad, cin_pad] += the plane conv's weight gradient, dbias (fp32 [cout],
+    optional) += the bias gradient (column sums of g); both summed in a fixed order."""
+    N, H, W, KH = planes
+    size = (dw_packed.shape[2], dw_packed.shape[1], N, H, W, KH, pix_per_block)
+    ws, nb = _ws("dlcs_conv2d_k3_wgrad", dw_packed.device, *size)
+    _call2d("dlcs_conv2d_k3_wgrad", p(x), cin, x.shape[-1], dw_packed.shape[2], p(g), cout, g.shape[-1],
+            dw_packed.shape[1], p(dw_packed), p(dbias), N, H, W, KH, pix_per_block, p(ws), nb, S())
+    return dw_packed
+
+
+def conv2d_unpack_grad(dw_packed, grad, cout, cin, accumulate=1):
+    KH = dw_packed.shape[0] // 3
+    _call2d("dlcs_conv2d_unpack_wgrad", p(dw_packed), p(grad), cout, cin, dw_packed.shape[1], dw_packed.shape[2], KH,
+            int(accumulate), S())
+    return grad

@@ -26,6 +26,30 @@ from ..mri import lowrank
 from ..mri.algorithms import ConjugateGradient, PowerMethod
 
 
+class _DenseGrad(torch.autograd.Function):
+    """Identity whose gradient is made contiguous.  The gradient of a CNN's input leaves the
+    permutes of cnn_update_L / cnn_update_R as a strided view.  Under the re-entrant checkpoint
+    an output of the segment that nothing reads downstream (L and R of the MoDL v2 state) gets a
+    materialised, contiguous zero gradient first, so the sum with that view is contiguous, while
+    the single backward pass hands the view on; torch's reductions in the CG backward then add
+    in another order and the two modes differ in the last fp32 bits.  In compute dtype bf16 such
+    a difference moves gradient elements across a bf16 rounding boundary in the next CNN
+    (2^-8 each), so there both modes are given the same layout; fp32 keeps what it had."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.contiguous()
+
+
+def _dense_grad(x):
+    from .swin3D import get_compute_dtype
+    return _DenseGrad.apply(x) if get_compute_dtype() == torch.bfloat16 and x.requires_grad else x
+
+
 class UnrolledLRNet(nn.Module):
     """dslr:18-170 -- abstract unrolled network over (L, R)."""
 
@@ -85,6 +109,7 @@ class UnrolledLRNet(nn.Module):
 
     def cnn_update_L(self, L, iter):
         """dslr:139-153"""
+        L = _dense_grad(L)
         num_blocks = L.shape[0]
         shape_before = (num_blocks, self.num_basis * self.num_emaps, self.block_size, self.block_size)
         shape_after = (num_blocks, self.num_basis, self.num_emaps * (self.block_size ** 2))
@@ -94,7 +119,7 @@ class UnrolledLRNet(nn.Module):
 
     def cnn_update_R(self, R, iter):
         """dslr:155-164"""
-        return self.temporal_cnn_update[iter](R.permute(0, 2, 1)).permute(0, 2, 1)
+        return self.temporal_cnn_update[iter](_dense_grad(R).permute(0, 2, 1)).permute(0, 2, 1)
 
     def _unroll(self, update, state):
         """The loop of dslr:245-250: one (checkpointed) update per unroll over the state tuple."""

@@ -13,6 +13,9 @@ sequences [N, C, T'] are laid out as the (depth, height) positions of one
 and centre height tap of a 27-tap weight, so sequences do not mix.  The W border is the
 conv's own zero padding only if the grid is not padded along W: T' = T + 2 pad_size
 must be a multiple of 4 (NotImplementedError otherwise).
+
+Compute dtype bf16 runs resnet2d's plane node with KH = 1: the N sequences are the rows
+[N T', ld] themselves, 3 taps along time, any T' <= 256 and no padding of N.
 """
 import torch
 from torch import nn
@@ -42,6 +45,7 @@ class ResNet(r2d.ResNet):
     NAME, BLOCK, RES = "ResNet1D", ConvBlock, ResBlock
     EMBED = staticmethod(_embed_w)
     CENTRE = staticmethod(lambda g3: g3[:, :, 1, 1])
+    KH = 1
 
     def forward(self, input):
         N, C, T = input.shape
@@ -49,6 +53,11 @@ class ResNet(r2d.ResNet):
             raise NotImplementedError("dl_cs HIP ResNet1D: CIRCULAR_PAD: True (configs/config_dslr.yaml)")
         pad = self.pad_size
         Tp = T + 2 * pad
+        if r2d.get_compute_dtype() == torch.bfloat16:
+            u = torch.cat((input.real, input.imag), dim=1)
+            u = nn.functional.pad(u, (pad, pad), mode='circular')
+            o = self._run(u.unsqueeze(2))[:, :, 0, pad:Tp - pad]
+            return torch.complex(o[:, :C].contiguous(), o[:, C:].contiguous())
         if Tp % 4:
             raise NotImplementedError(f"dl_cs HIP ResNet1D: T + 2 pad_size = {Tp} must be a multiple of 4 (the conv grid)")
         u = torch.cat((input.real, input.imag), dim=1)                              # r1d:225-229

@@ -21,6 +21,15 @@ centre-tap slices of the 27-tap gradient.  The zero taps cost 3x the multiplies 
 
 `embedded_forward` / `embedded_backward` take a real [1, C, D, H, W] tensor and the
 embedding; resnet1d.py reuses them.
+
+Compute dtype bf16 (swin3D.set_compute_dtype) runs the same algebra as a second node,
+_PlaneFn, on the plane conv (dlcs_conv2d_k3 / dlcs_conv2d_k3_wgrad, csrc/conv2d.hip): the
+blocks are independent planes of channels-last rows [N b b, ld], any b <= 16, 9 taps (3 for
+the 1-D net) instead of 27.  r, t and every feature-width gradient are stored in bf16; the
+convs accumulate in fp32, add bias and residual in fp32 and round once.  Weights, weight and
+bias gradients, u, the final conv's output, the init dgrad's output and the complex boundary
+stay fp32, and so do the two residuals that cross the boundary (+ u forward, + go backward).
+The weight and bias gradients are summed in a fixed order: two runs give the same bits.
 """
 import torch
 from torch import nn
@@ -150,6 +159,95 @@ def embedded_backward(P, names, sv, gout, grads, embed, centre):
     return from_blocked(du, sv["shape"])
 
 
+# ------------------------------------------------------------------ the bf16 node (plane conv)
+def _to_rows(x, ld):
+    """fp32 [N, C, H, W] -> channels-last rows [N H W, ld] (zero slack columns)."""
+    N, C, H, W = x.shape
+    rows = torch.zeros((N * H * W, ld), dtype=torch.float32, device=x.device)
+    rows.view(N, H, W, ld)[..., :C] = x.permute(0, 2, 3, 1)
+    return rows
+
+
+def _from_rows(rows, shape):
+    N, C, H, W = shape
+    return rows.view(N, H, W, rows.shape[-1])[..., :C].permute(0, 3, 1, 2).contiguous()
+
+
+def _wgrad_pix(rows):
+    """Pixel range per workgroup of the plane conv's weight gradient: about 48 ranges (each
+    is a launch of KH 3 workgroups per 128 output channels and one partial slab to add)."""
+    return min(16384, max(256, (rows // 48 + 63) // 64 * 64))
+
+
+def plane_forward(P, names, x, KH):
+    """x fp32 [N, C, H, W] (KH 3: N planes) or [N, C, 1, W] (KH 1: N sequences) -> (out, saved)."""
+    N, C, H, W = x.shape
+    planes = (N, H, W, KH)
+    ld = _pad8(C)
+    F = P[names["init_w"]].shape[0]
+    Fld = _pad8(F)
+    u32 = _to_rows(x, ld)                                     # the input residual is added unrounded
+    u = K.cast(u32, torch.bfloat16)
+    conv = lambda a, cin, w, cout, out_ld, **kw: K.conv2d(a, cin, K.conv2d_pack(P[w], 0), cout, out_ld, planes, **kw)
+    r = [conv(u, C, names["init_w"], F, Fld, bias=P[names["init_b"]], relu_out=1)]
+    ts = []
+    for wa, ba, wb, bb in names["blocks"]:
+        t = conv(r[-1], F, wa, F, Fld, bias=P[ba], relu_out=1)
+        ts.append(t)
+        r.append(conv(t, F, wb, F, Fld, bias=P[bb], res=r[-1], relu_out=1))
+    o = conv(r[-1], F, names["final_w"], C, ld, bias=P[names["final_b"]], res=u32, out_dtype=torch.float32)
+    return _from_rows(o, tuple(x.shape)), dict(u=u, r=r, ts=ts, planes=planes, C=C, F=F, ld=ld, Fld=Fld,
+                                               shape=tuple(x.shape))
+
+
+def plane_backward(P, names, sv, gout, grads):
+    """Backward of plane_forward; grads[name] += the weight and bias gradients (fp32)."""
+    planes, C, F, ld, Fld = sv["planes"], sv["C"], sv["F"], sv["ld"], sv["Fld"]
+    rows = planes[0] * planes[1] * planes[2]
+    r, ts, u = sv["r"], sv["ts"], sv["u"]
+    pix = _wgrad_pix(rows)
+
+    def wgrad(x, cin, g, cout, wname, bname):
+        dwp = torch.zeros((planes[3] * 3, K.pad32(cout), K.pad32(cin)), dtype=torch.float32, device=g.device)
+        K.conv2d_wgrad(x, cin, g, cout, planes, dwp, pix_per_block=pix, dbias=grads[bname])
+        K.conv2d_unpack_grad(dwp, grads[wname], cout, cin)
+
+    dgrad = lambda g, cout_w, w, cin_w, out_ld, **kw: K.conv2d(g, cout_w, K.conv2d_pack(P[w], 1), cin_w, out_ld, planes, **kw)
+    go32 = _to_rows(gout, ld)                                                       # the + u path, unrounded
+    go = K.cast(go32, torch.bfloat16)
+    wgrad(r[-1], F, go, C, names["final_w"], names["final_b"])
+    g = dgrad(go, C, names["final_w"], F, Fld, mask=r[-1])                          # dL/d o_L (through relu)
+    for k in reversed(range(len(ts))):
+        wa, ba, wb, bb = names["blocks"][k]
+        wgrad(ts[k], F, g, F, wb, bb)
+        gt = dgrad(g, F, wb, F, Fld, mask=ts[k])
+        wgrad(r[k], F, gt, F, wa, ba)
+        g = dgrad(gt, F, wa, F, Fld, res=g, mask=None)                              # dL/d r_k (conv + residual)
+        g = K.relu_grad(g, r[k])                                                    # dL/d o_k
+    wgrad(u, C, g, F, names["init_w"], names["init_b"])
+    du = dgrad(g, F, names["init_w"], C, ld, res=go32, out_dtype=torch.float32)
+    return _from_rows(du, sv["shape"])
+
+
+class _PlaneFn(torch.autograd.Function):
+    """One node per network call in compute dtype bf16: x fp32 [N, C, H, W]."""
+
+    @staticmethod
+    def forward(ctx, x, meta, *plist):
+        P = dict(zip(meta["order"], plist))
+        out, sv = plane_forward(P, meta["names"], x.to(torch.float32), meta["KH"])
+        ctx.state = (P, sv, meta)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        P, sv, meta = ctx.state
+        grads = {n: torch.zeros_like(p) for n, p in P.items()}
+        gx = plane_backward(P, meta["names"], sv, gout.to(torch.float32), grads)
+        ctx.state = None
+        return (gx, None) + tuple(grads[n] for n in meta["order"])
+
+
 class _EmbeddedFn(torch.autograd.Function):
     """One node per network call: x fp32 [1, C, D, H, W]."""
 
@@ -181,6 +279,7 @@ class ResNet(nn.Module):
     NAME, BLOCK, RES = "ResNet2D", ConvBlock, ResBlock
     EMBED = staticmethod(_embed_hw)
     CENTRE = staticmethod(lambda g3: g3[:, :, 1])
+    KH = 3             # tap rows of the plane conv (the bf16 node)
 
     def __init__(self, num_resblocks, in_chans, chans, kernel_size, use_complex_layers=False, circular_pad=False):
         super().__init__()
@@ -196,9 +295,11 @@ class ResNet(nn.Module):
         self.final_layer = self.BLOCK(chans, in_chans, kernel_size, act_type='relu')
 
     def _run(self, x):
-        """x fp32 [1, C, D, H, W] through the fused node."""
-        if get_compute_dtype() != torch.float32:
-            raise NotImplementedError(f"dl_cs HIP {self.NAME}: fp32 (the generic conv kernels)")
+        """x through the fused node of the compute dtype: fp32 [1, C, D, H, W] (the embedding),
+        bf16 [N, C, H, W] (planes; the 1-D net passes [N, C, 1, T'])."""
+        dtype = get_compute_dtype()
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise NotImplementedError(f"dl_cs HIP {self.NAME}: compute dtype float32 or bfloat16 (got {dtype})")
         if not x.is_cuda:
             raise RuntimeError(f"dl_cs HIP {self.NAME} needs GPU tensors (no CPU fallback in the product path)")
         params = dict(self.named_parameters())
@@ -207,12 +308,19 @@ class ResNet(nn.Module):
         (iw, ib), (fw, fb) = c("init_layer"), c("final_layer")
         blocks = [c(f"res_blocks.{k}.layers.0") + c(f"res_blocks.{k}.layers.1") for k in range(len(self.res_blocks))]
         names = dict(init_w=iw, init_b=ib, final_w=fw, final_b=fb, blocks=blocks)
+        if dtype == torch.bfloat16:
+            meta = dict(order=order, names=names, KH=self.KH)
+            return _PlaneFn.apply(x, meta, *[params[n] for n in order])
         meta = dict(order=order, names=names, embed=self.EMBED, centre=self.CENTRE)
         return _EmbeddedFn.apply(x, meta, *[params[n] for n in order])
 
     def forward(self, input):
-        """input complex64 [N, C, b, b] -> the same shape (b a multiple of 4)."""
+        """input complex64 [N, C, b, b] -> the same shape (fp32: b a multiple of 4; bf16: any b <= 16)."""
         N, C, H, W = input.shape
+        if get_compute_dtype() == torch.bfloat16:
+            u = torch.cat((input.real, input.imag), dim=1)
+            o = self._run(u)
+            return torch.complex(o[:, :C].contiguous(), o[:, C:].contiguous())
         if H % 4 or W % 4:
             raise NotImplementedError(f"dl_cs HIP {self.NAME}: block size a multiple of 4 (the conv grid)")
         u = torch.cat((input.real, input.imag), dim=1)                              # r2d:225-231

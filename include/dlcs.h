@@ -834,6 +834,53 @@ int dlcs_lr_project_l(const void* image, const void* R, const float* weights, co
 int dlcs_lr_project_r(const void* image, const void* L, const float* weights, const float* win, int divide, void* out,
                       int64_t E, int64_t T, int64_t Y, int64_t X, int64_t b, int64_t r, dlcs_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Plane conv (conv2d.hip): the bf16 k = 3 convolution of the DSLR family's 2-D and 1-D
+ * ResNets (resnet2d.py, resnet1d.py) over independent planes, fp32 accumulation.
+ *   KH = 3: N planes [H][W], taps (dy, dx); the H and W borders are zero padding
+ *   KH = 1: N H sequences of length W, taps dx only; the W borders are zero padding
+ * Planes never mix.  Operands are bf16 channels-last rows [N H W, ld], row = (n H + h) W + w
+ * (not patch-blocked: no multiple-of-4 rule), ld >= channels and ld % 8 == 0, 16-B aligned.
+ * Input and gout columns >= their channel count are never read as channels (they may hold
+ * anything); output columns >= cout are left untouched.
+ *   out[row, co] = epi(conv(in)[row, co] + bias[co])
+ *   epi: times (mask[row, co] > 0) if mask (bf16, a stored post-ReLU activation: ReLU backward);
+ *        + res_scale * residual[row, co] (bf16 or fp32, res_dtype); then ReLU if relu_out
+ * out is bf16 or fp32 (out_dtype).  bias, mask and residual may be NULL.
+ * dgrad = the same call on weights packed with mode 1.
+ *   dlcs_conv2d_pack_weights: torch weight w fp32 [cout][cin][KH][3] -> bf16
+ *     mode 0: [KH 3][rows_pad = cout_pad][cols_pad = cin_pad];
+ *     mode 1 (dgrad): [KH 3][rows_pad = cin_pad][cols_pad = cout_pad], taps flipped;
+ *     the pads are zero.  *_pad: the channel count rounded up to 32.
+ *   dlcs_conv2d_k3_wgrad: dw_packed fp32 [KH 3][cout_pad][cin_pad] +=
+ *     sum_pixels gout[p, co] in[p + off(tap), ci].  The pixels are split into ranges of
+ *     pix_per_block (rounded up to 64; <= 0: 4096), one workgroup per (range, tap, 128 co);
+ *     every workgroup stores its partial slab to the workspace and a second launch adds the
+ *     slabs in range order: no float atomics, the same input gives the same bits.  dbias
+ *     (optional, fp32 [cout]) += sum_pixels gout[p, co], the conv's bias gradient, from the g
+ *     tiles the tap-0 workgroups hold, summed the same way (dlcs_colsum adds its workgroups'
+ *     partial sums with atomics, so its last bits depend on their order).  More than
+ *     65535 ranges: DLCS_ERR_UNSUPPORTED_SIZE.  Too small a workspace: DLCS_ERR_WORKSPACE.
+ *   dlcs_conv2d_unpack_wgrad: grad fp32 [cout][cin][KH][3] (+)= dw_packed.
+ * Supported: KH in {3, 1}; N >= 1; KH = 3: 1 <= H, W <= 16 (lowrank.hip's b <= 16);
+ * KH = 1: H >= 1, 1 <= W <= 256 (T <= 32 plus any circular pad); N H W < 2^31;
+ * 1 <= cin, cout <= 256.  Beyond: DLCS_ERR_UNSUPPORTED_SIZE before any launch, nothing is
+ * written.  No allocation, no global state.                                             */
+int dlcs_conv2d_k3(const void* in, int64_t cin, int64_t cin_ld, const void* wpacked, int64_t cin_pad,
+                   const float* bias, void* out, int out_dtype, int64_t cout, int64_t cout_pad, int64_t cout_ld,
+                   int64_t N, int64_t H, int64_t W, int KH, const void* mask, int64_t mask_ld,
+                   const void* residual, int res_dtype, int64_t res_ld, float res_scale, int relu_out,
+                   dlcs_stream_t stream);
+int dlcs_conv2d_pack_weights(const float* w, void* packed, int64_t cout, int64_t cin, int64_t rows_pad,
+                             int64_t cols_pad, int KH, int mode, dlcs_stream_t stream);
+size_t dlcs_conv2d_k3_wgrad_workspace_bytes(int64_t cin_pad, int64_t cout_pad, int64_t N, int64_t H, int64_t W, int KH,
+                                            int64_t pix_per_block);
+int dlcs_conv2d_k3_wgrad(const void* in, int64_t cin, int64_t cin_ld, int64_t cin_pad, const void* gout, int64_t cout,
+                         int64_t g_ld, int64_t cout_pad, float* dw_packed, float* dbias, int64_t N, int64_t H, int64_t W,
+                         int KH, int64_t pix_per_block, void* workspace, size_t workspace_bytes, dlcs_stream_t stream);
+int dlcs_conv2d_unpack_wgrad(const float* dw_packed, float* grad, int64_t cout, int64_t cin, int64_t cout_pad,
+                             int64_t cin_pad, int KH, int accumulate, dlcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

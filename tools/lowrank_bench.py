@@ -9,9 +9,10 @@ from them at the shipped configuration (configs/config_dslr.yaml): E, T, Y, X = 
      fused (dlcs_lr_compose, dlcs_sense_normal, dlcs_lr_project_l) against unfused
      (torch.bmm, dlcs_lr_combine, dlcs_sense_normal, dlcs_lr_extract, torch.bmm) on the same
      inputs, alternating; and their outputs are compared (NRMSE);
-  c. one forward + backward of the 2-D and of the 1-D CNN (2 resblocks, 128 features, on the
-     generic conv3d_k3 kernels with the 3 x 3 / 3-tap weights embedded in 27 taps) beside one
-     10-step CG solve for L (11 normal applications).
+  c. one forward + backward of the 2-D and of the 1-D CNN (2 resblocks, 128 features) in both
+     compute dtypes -- fp32 on the generic conv3d_k3 kernels with the 3 x 3 / 3-tap weights
+     embedded in 27 taps, bf16 on the plane conv (csrc/conv2d.hip) -- beside one 10-step CG
+     solve for L (11 normal applications).
 
 One process; the variants alternate inside every round; each sample is HIP events around
 `reps` calls after a warm-up; median and minimum over the rounds.  --markdown FILE writes the
@@ -116,8 +117,9 @@ def main():
     x2 = crandn(N, r * E, b, b).requires_grad_()
     x1 = crandn(N, r, Tt).requires_grad_()
 
-    def train(net, x):
+    def train(net, x, dtype=torch.float32):
         def fn():
+            swin3D.set_compute_dtype(dtype)                   # read by the network at every call
             net.zero_grad(set_to_none=True)
             x.grad = None
             torch.sum(net(x).abs() ** 2).backward()
@@ -127,17 +129,23 @@ def main():
         with torch.no_grad():
             normal = lambda q: lr._project_l_raw(op, A.normal(lr._compose_raw(op, q, R, True)[None], 0.0)[0], R, False)
             return ConjugateGradient(normal, args.cg_steps)(L, lr._project_l_raw(op, img, R, False))
-    res = interleaved({"cnn2d_fwd_bwd": train(net2, x2), "cnn1d_fwd_bwd": train(net1, x1), "cg_solve_L": cg},
+    bf = torch.bfloat16
+    res = interleaved({"cnn2d_fwd_bwd": train(net2, x2), "cnn2d_fwd_bwd_bf16": train(net2, x2, bf),
+                       "cnn1d_fwd_bwd": train(net1, x1), "cnn1d_fwd_bwd_bf16": train(net1, x1, bf), "cg_solve_L": cg},
                       args.rounds, max(1, args.reps // 5))
+    swin3D.set_compute_dtype(torch.float32)
     for k, (med, mn) in res.items():
         emit(dict(what="unroll_part", part=k, median_us=med, min_us=mn), args.out)
-    md += ["", "| part of one unroll | median ms | min ms |", "|---|---|---|",
+    ms = lambda k: f"{res[k][0] / 1e3:.2f} | {res[k][1] / 1e3:.2f}"
+    ratio = lambda k: f"{res[k][0] / res[k + '_bf16'][0]:.2f}"
+    md += ["", "| part of one unroll | fp32 median ms | fp32 min ms | bf16 median ms | bf16 min ms | fp32 / bf16 |",
+           "|---|---|---|---|---|---|",
            f"| 2-D CNN forward + backward ([{N}, {2 * r * E}, {b}, {b}], {args.features} features, {args.resblocks} "
-           f"resblocks) | {res['cnn2d_fwd_bwd'][0] / 1e3:.2f} | {res['cnn2d_fwd_bwd'][1] / 1e3:.2f} |",
-           f"| 1-D CNN forward + backward ([{N}, {2 * r}, {Tt} + {2 * net1.pad_size}]) | {res['cnn1d_fwd_bwd'][0] / 1e3:.2f} | "
-           f"{res['cnn1d_fwd_bwd'][1] / 1e3:.2f} |",
+           f"resblocks) | {ms('cnn2d_fwd_bwd')} | {ms('cnn2d_fwd_bwd_bf16')} | {ratio('cnn2d_fwd_bwd')} |",
+           f"| 1-D CNN forward + backward ([{N}, {2 * r}, {Tt} + {2 * net1.pad_size}]) | {ms('cnn1d_fwd_bwd')} | "
+           f"{ms('cnn1d_fwd_bwd_bf16')} | {ratio('cnn1d_fwd_bwd')} |",
            f"| one {args.cg_steps}-step CG solve for L, forward ({args.cg_steps + 1} normal applications) | "
-           f"{res['cg_solve_L'][0] / 1e3:.2f} | {res['cg_solve_L'][1] / 1e3:.2f} |"]
+           f"{ms('cg_solve_L')} | | | |"]
     text = "\n".join(md) + "\n"
     print(text)
     if args.markdown:
