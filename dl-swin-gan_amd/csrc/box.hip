@@ -21,6 +21,11 @@
 //   4 columns as one 16-B store when C % 4 == 0, ld % 4 == 0 and the base is 16-B
 //   aligned (se.hip's rule), else one float.  It reads no memory.  bf16 rows: 8 columns per
 //   16-B store when C % 8 == 0, ld % 8 == 0 and the base is aligned, else one element.
+// * dlcs_box_shift -- the box moved by a voxel shift (sd, sh, sw) inside the padded grid and
+//   its adjoint: the centre crop of the DiT / Latte unpatchify2, whose subpatches the final
+//   Linear scatters at the origin.  A gather per dst row (one thread per row and 16-B column
+//   chunk, rows in blocked order), +0.0 on the rows without a source, optionally + a residual
+//   row and a ReLU (DiTResNet's relu(DiT(res) + res)).
 #include "dlcs_common.h"
 
 namespace {
@@ -135,6 +140,57 @@ __global__ void __launch_bounds__(256) box_zero_kernel(T* x, long ld, int nch, Z
     }
 }
 
+struct ShiftDims {
+    int Dp, Hp, Wp, D, H, W, sd, sh, sw, nch;
+    long rows, ld_src, ld_dst, ld_res;
+};
+
+// one thread per (row of the padded grid, chunk of V columns), rows in blocked order so a
+// wave's stores are contiguous; the source row is a box_row() gather.  TR false: a box row
+// reads the voxel shifted by (+sd, +sh, +sw) (plus its own row of res, then the ReLU), a slack
+// row gets +0.0.  TR true (the adjoint): a row reads the voxel at (-sd, -sh, -sw) when that
+// is a box voxel, else gets +0.0.
+template <int V, bool TR>
+__global__ void __launch_bounds__(256) box_shift_kernel(const float* src, float* dst, const float* res, int relu,
+                                                        ShiftDims s) {
+    const long total = s.rows * s.nch;
+    const int nY = s.Hp >> 2, nX = s.Wp >> 2, nT = s.Dp >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / s.nch;
+        const long col = (i - r * s.nch) * V;
+        const int in = (int)(r & 63);
+        long q = r >> 6;
+        const int x = (int)(q % nX) * 4 + (in & 3); q /= nX;
+        const int y = (int)(q % nY) * 4 + ((in >> 2) & 3); q /= nY;
+        const int t = (int)(q % nT) * 4 + (in >> 4);
+        const int b = (int)(q / nT);
+        const int ts = TR ? t - s.sd : t + s.sd, ys = TR ? y - s.sh : y + s.sh, xs = TR ? x - s.sw : x + s.sw;
+        const bool live = TR ? (ts >= 0 && ts < s.D && ys >= 0 && ys < s.H && xs >= 0 && xs < s.W)
+                             : (t < s.D && y < s.H && x < s.W);
+        float* d = dst + r * s.ld_dst + col;
+        if constexpr (V > 1) {
+            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (live) {
+                v = *reinterpret_cast<const f32x4*>(src + box_row(b, ts, ys, xs, s.Dp, s.Hp, s.Wp) * s.ld_src + col);
+                if (res) v += *reinterpret_cast<const f32x4*>(res + r * s.ld_res + col);
+                if (relu) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+                }
+            }
+            *reinterpret_cast<f32x4*>(d) = v;
+        } else {
+            float v = 0.0f;
+            if (live) {
+                v = src[box_row(b, ts, ys, xs, s.Dp, s.Hp, s.Wp) * s.ld_src + col];
+                if (res) v += res[r * s.ld_res + col];
+                if (relu) v = fmaxf(v, 0.0f);
+            }
+            *d = v;
+        }
+    }
+}
+
 unsigned box_blocks(long n) {
     long g = (n + 255) / 256;
     if (g > 8192) g = 8192;
@@ -233,6 +289,32 @@ int dlcs_box_zero(float* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_
         hipLaunchKernelGGL((box_zero_kernel<float, 4>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
     else
         hipLaunchKernelGGL((box_zero_kernel<float, 1>), grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, nch, z);
+    return dlcs_launch_status();
+}
+
+int dlcs_box_shift(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int64_t C, int64_t B, int64_t Dp,
+                   int64_t Hp, int64_t Wp, int64_t D, int64_t H, int64_t W, int64_t sd, int64_t sh, int64_t sw,
+                   int transpose, const float* residual, int64_t ld_res, int relu, dlcs_stream_t stream) {
+    DLCS_CHECK_ARG(src && dst && (const float*)dst != src && B > 0 && C > 0 && ld_src >= C && ld_dst >= C && D > 0 &&
+                   H > 0 && W > 0 && sd >= 0 && sh >= 0 && sw >= 0 && (!residual || ld_res >= C) &&
+                   (!transpose || (!residual && !relu)));
+    long ld_max = ld_src > ld_dst ? ld_src : ld_dst;
+    if (residual && ld_res > ld_max) ld_max = ld_res;
+    // the shifted box stays inside the padded grid: D + sd <= Dp, ... (no overflow: all < 2^30 is checked first)
+    if (!box_grid_ok(Dp, Hp, Wp, D, H, W) || sd >= (1L << 30) || sh >= (1L << 30) || sw >= (1L << 30) ||
+        D + sd > Dp || H + sh > Hp || W + sw > Wp || B > (1L << 20) || C > (1L << 20) || ld_max >= (1L << 30) ||
+        B * Dp * Hp * Wp > (1L << 62) / ld_max)
+        return DLCS_ERR_UNSUPPORTED_SIZE;
+    const bool vec = C % 4 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0 && al16(src) && al16(dst) &&
+                     (!residual || (ld_res % 4 == 0 && al16(residual)));
+    ShiftDims s{(int)Dp, (int)Hp, (int)Wp, (int)D, (int)H, (int)W, (int)sd, (int)sh, (int)sw, (int)(vec ? C / 4 : C),
+                B * Dp * Hp * Wp, (long)ld_src, (long)ld_dst, (long)ld_res};
+    const dim3 grid(box_blocks(s.rows * s.nch)), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (vec && transpose) hipLaunchKernelGGL((box_shift_kernel<4, true>), grid, block, 0, st, src, dst, residual, relu, s);
+    else if (vec) hipLaunchKernelGGL((box_shift_kernel<4, false>), grid, block, 0, st, src, dst, residual, relu, s);
+    else if (transpose) hipLaunchKernelGGL((box_shift_kernel<1, true>), grid, block, 0, st, src, dst, residual, relu, s);
+    else hipLaunchKernelGGL((box_shift_kernel<1, false>), grid, block, 0, st, src, dst, residual, relu, s);
     return dlcs_launch_status();
 }
 

@@ -111,6 +111,7 @@ SIGNATURES = {
     "dlcs_box_post": [_P, _P] + [_I64] * 10 + [_P],
     "dlcs_box_post_bwd": [_P, _P] + [_I64] * 10 + [_P],
     "dlcs_box_zero": [_P] + [_I64] * 9 + [_P],
+    "dlcs_box_shift": [_P, _I64, _P] + [_I64] * 12 + [_INT, _P, _I64, _INT, _P],
     "dlcs_box_pre_bf16": [_P, _P] + [_I64] * 10 + [_P],
     "dlcs_box_post_bwd_bf16": [_P, _P] + [_I64] * 10 + [_P],
     "dlcs_box_zero_bf16": [_P] + [_I64] * 9 + [_P],

@@ -12,8 +12,9 @@ autograd node whose forward and hand-scheduled backward are HIP kernels
 
 Configurations outside the HIP path raise NotImplementedError: complex layers,
 NUM_RESBLOCKS != 0 is allowed (it only changes the time padding), learn_sigma,
-grids whose padded T is not a multiple of 4 or whose Y, X are not multiples of
-4, head dims > 32, and the bf16 compute dtype (the DiT path is fp32).
+head dims > 32, and the bf16 compute dtype (the DiT path is fp32).  Any grid size
+runs: the patch embed's zero pad and unpatchify2's centre crop (dit:30-53,
+:117-122, :539-541) are the engine's "Any grid size" path.
 """
 import collections.abc
 import itertools

@@ -16,8 +16,9 @@ declares an SFE and a final ConvBlock that its forward never calls (lat:875,
 
 Configurations outside the HIP path raise NotImplementedError: complex layers,
 learn_sigma, extras != 1 (label / text conditioning is not reachable from
-LatteNet), grids whose padded T is not a multiple of 4 or whose Y, X are not
-multiples of 4, head dims > 32, an odd layer count, and the bf16 compute dtype.
+LatteNet), head dims > 32, an odd layer count, and the bf16 compute dtype.  Any
+grid size runs (the patch embed's zero pad and unpatchify2's centre crop,
+lat:126-129, :193-214, :450-475: latte_engine's "Any grid size").
 """
 import collections.abc
 import itertools

@@ -703,6 +703,17 @@ def box_zero(x, C, grid, box):
     return x
 
 
+def box_shift(src, C, grid, box, shift, transpose=False, out=None, res=None, relu=False):
+    """out[row(v)][:C] = src[row(v + shift)][:C] (+ res[row(v)][:C], then ReLU) on the voxels v of
+    the box, +0.0 on slack rows; transpose: the adjoint, out[row(v + shift)] = src[row(v)] and
+    +0.0 on every other row of grid (dlcs_box_shift; src, out, res fp32 [rows of grid, ld])."""
+    if out is None:
+        out = empty(src.shape, torch.float32, src.device)
+    call("dlcs_box_shift", p(src), src.shape[-1], p(out), out.shape[-1], C, *grid, *box[1:], *shift, int(transpose),
+         p(res), res.shape[-1] if res is not None else 0, int(relu), S())
+    return out
+
+
 def relu_grad(g, a):
     """g *= (a > 0) in place (a: stored post-ReLU activation, same element count)."""
     assert g.numel() == a.numel()

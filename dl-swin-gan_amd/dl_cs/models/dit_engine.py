@@ -1,7 +1,8 @@
 """HIP forward / hand-scheduled backward of the DiT regularizers (DiTResNet,
 DiTNet; dit = dl_cs/models/DiT.py), one autograd node per network call.
 
-Layouts (fp32; B samples, time padded to Tp = T + 2 pad, Y, X multiples of 4):
+Layouts (fp32; B samples, time padded to Tp = T + 2 pad; any Tp, Y, X -- a grid that is no
+multiple of 4 runs in the grid rounded up, see Geo and "Any grid size" below):
   * full-resolution activations in the patch-blocked channels-last layout of the
     Swin path (row(b,t,y,x) = patch-of-4x4x4 * 64 + (t%4) 16 + (y%4) 4 + x%4), so
     a (2,4,4) DiT patch is 32 consecutive rows: the patch embed (dit:103, :124) is
@@ -16,6 +17,13 @@ Gated residual branches g * (x W^T + b) (dit:338, :345, :348) run as one GEMM on
 gate-scaled weights (dlcs_scale_rows); their gate / weight / bias gradients come
 from the unscaled dW GEMM (dlcs_gated_linear_grad).  adaLN-modulated LayerNorms
 (dit:22-23) are dlcs_layernorm with gamma = 1 + scale, beta = shift.
+
+Any grid size: the reference's patch embed zero-pads the end of each axis up to the
+(2, 4, 4) patch (dit:30-53, :117-122) and unpatchify2 crops the centre (dit:539-541), so
+the output is shifted by ceil(pad / 2) against the input.  Here the tokens are exactly the
+reference's (Geo.sub2tok skips every other subpatch of the rounded-up grid), the rows
+outside the box hold zeros wherever they are read, and the crop is dlcs_box_shift after
+the final Linear (its adjoint in the backward), launched only when a shift is non-zero.
 """
 
 import os
@@ -101,22 +109,41 @@ def _dev_i32(a, device):
 _GEO = {}
 
 
+def _ceil_div(a, b):
+    return -(-a // b)
+
+
 class Geo:
-    """Index maps of one (B, Tp, Y, X) geometry (host-built once, cached)."""
+    """Index maps of one (B, Tp, Y, X) geometry (host-built once, cached).
+
+    Three grids: the box (B, Tp, Y, X) of the call; the layout grid `grid` = (B, Dp, Hp, Wp),
+    each axis rounded up to 4, whose patch-blocked rows (V of them, S = V / 32 subpatches)
+    hold the box at the origin; and the reference's token grid (F, Hh, Ww) = ceil of the box
+    over the (2, 4, 4) patch (dit:30-53), M tokens.  sub2tok is -1 on the subpatches of the
+    layout grid that are no token (the second half of the last 4-frame block when F is
+    odd); `shift` is where unpatchify2's centre crop starts (dit:539-541), ceil(pad / 2) per
+    axis, and `slack` says whether the layout grid has rows outside the box."""
 
     def __init__(self, B, Tp, Y, X, device):
         self.B, self.Tp, self.Y, self.X = B, Tp, Y, X
-        self.F, self.Hh, self.Ww = Tp // 2, Y // 4, X // 4
-        self.V = B * Tp * Y * X
+        self.box = (B, Tp, Y, X)
+        self.grid = (B, K.pad4(Tp), K.pad4(Y), K.pad4(X))
+        self.slack = self.grid != self.box
+        self.F, self.Hh, self.Ww = _ceil_div(Tp, 2), _ceil_div(Y, 4), _ceil_div(X, 4)
+        self.shift = (_ceil_div(2 * self.F - Tp, 2), _ceil_div(4 * self.Hh - Y, 2), _ceil_div(4 * self.Ww - X, 2))
+        self.shifted = any(self.shift)
+        self.V = B * self.grid[1] * self.grid[2] * self.grid[3]
+        self.S = self.V // 32
         self.M = B * self.F * self.Hh * self.Ww
         self.Mb = self.M // B
         F, Hh, Ww = self.F, self.Hh, self.Ww
         b, f, h, w = np.meshgrid(np.arange(B), np.arange(F), np.arange(Hh), np.arange(Ww), indexing="ij")
         tok = ((b * F + f) * Hh + h) * Ww + w                          # reference token order (b, f, h, w)
-        sub = (((b * (Tp // 4) + f // 2) * Hh + h) * Ww + w) * 2 + f % 2   # 32-row subpatch of the blocked layout
+        nT = self.grid[1] // 4
+        sub = (((b * nT + f // 2) * Hh + h) * Ww + w) * 2 + f % 2        # 32-row subpatch of the blocked layout
         tim = ((b * Hh + h) * Ww + w) * F + f                          # (b, h, w, f) order of flag-1 attention
         tok, sub, tim = tok.reshape(-1), sub.reshape(-1), tim.reshape(-1)
-        sub2tok = np.empty(self.M, np.int64)
+        sub2tok = np.full(self.S, -1, np.int64)
         sub2tok[sub] = tok
         tok2sub = np.empty(self.M, np.int64)
         tok2sub[tok] = sub
@@ -421,6 +448,37 @@ def block_backward(P, G, nb, sv, dy, sc, dsc, geo, heads, hd):
 
 
 # ---------------------------------------------------------------------------- whole network
+# Any grid size (shared with latte_engine).  A call whose box (B, Tp, Y, X) is no multiple of 4
+# runs on geo.grid, the box rounded up, as the conv trunks do (resnet3d.py "padded path"), but
+# makes tokens of the reference's token grid only (geo.sub2tok is -1 elsewhere: the GEMMs skip
+# those rows, gather_rows gives zeros).  The reference's patch embed zero-pads the end of each
+# axis, so everything the patch embed, a thin conv's dgrad / wgrad, a colsum or a weight
+# gradient reads must be zero on the slack rows: box_pre and box_post_bwd write zeros there,
+# box_shift writes zeros outside the (shifted) box, a ReLU-masked dgrad is zero wherever the
+# stored post-ReLU tensor is, and box_post / box_pre_bwd read the box only; what is left is
+# cleared with _zero.  Without slack the launches are those of the dlcs_swin_* path.
+def _pre(x, pad, geo):
+    return K.box_pre(x, pad, PAD_CIN, geo.grid) if geo.slack else K.swin_pre(x, torch.float32, pad, PAD_CIN)
+
+
+def _post(o, shape, pad, geo):
+    return K.box_post(o, shape, pad, geo.grid) if geo.slack else K.swin_post(o, shape, pad)
+
+
+def _post_bwd(gout, pad, geo):
+    return (K.box_post_bwd(gout, pad, PAD_CIN, geo.grid) if geo.slack else
+            K.swin_post_bwd(gout, torch.float32, pad, PAD_CIN))
+
+
+def _pre_bwd(du, shape, pad, geo):
+    return K.box_pre_bwd(du, shape, pad, geo.grid) if geo.slack else K.swin_pre_bwd(du, shape, pad)
+
+
+def _zero(t, C, geo):
+    """+0.0 on the slack rows of t in place (nothing without slack)."""
+    return K.box_zero(t, C, geo.grid, geo.box) if geo.slack else t
+
+
 def _patch_weights(P, n, D, ldsrc):
     """GEMM layouts of the patch embed [D][(kd, kh, kw)][c] (channel stride ldsrc) and of the
     final Linear for a thin (DiTNet) output: rows (p, q, r, c) at channel stride PAD_CIN."""
@@ -447,18 +505,16 @@ def regularizer_forward(P, n, x, t, labels, meta):
     B, E, T, Y, X = x.shape
     pad, depth, heads = meta["pad"], meta["depth"], meta["heads"]
     Tp = T + 2 * pad
-    if Tp % 4 or Y % 4 or X % 4:
-        raise NotImplementedError("dl_cs HIP DiT: T + 2 pad, Y and X must be multiples of 4")
     dev = x.device
-    grid = (B, Tp, Y, X)
     geo = Geo.get(B, Tp, Y, X, dev)
+    grid = geo.grid
     cin = 2 * E
     resid = meta["residual_convs"]
     D = P[n["pe_w"]].shape[0]
     hd = D // heads
     if hd > 32 or hd % 4 or D % heads:
         raise NotImplementedError(f"dl_cs HIP DiT: head dim {D}/{heads} must be <= 32 and a multiple of 4")
-    u = K.swin_pre(x.contiguous(), torch.float32, pad, PAD_CIN)                 # [V, 8]
+    u = _pre(x.contiguous(), pad, geo)                                          # [V, 8], zero on slack rows
     sv = dict(u=u, grid=grid, geo=geo, shape=(B, E, T, Y, X))
     if resid:
         col = _im2col(u, cin, grid, +1, _tld(D))                                  # [V, 108 (128)]
@@ -468,6 +524,7 @@ def regularizer_forward(P, n, x, t, labels, meta):
             res = _gemm_h3(col, Wsfe, D, bias=P[n["sfe_b"]])                     # [V, D]  SFE (dit:1339)
         else:
             res = K.linear(col, Wsfe.view(D, 27 * cin), bias=P[n["sfe_b"]])
+        _zero(res, D, geo)                # the bias and the box's neighbours: the embed's pad, and `+ res`, read zeros
         sv.update(col=col, Wsfe=Wsfe, res=res)
         src, ldsrc = res, D
     else:
@@ -478,9 +535,9 @@ def regularizer_forward(P, n, x, t, labels, meta):
     pos = K.gather_rows(P[n["pos"]].view(-1, D), pos_idx, geo.M, torch.float32)
     tok = _empty((geo.M, D), dev)
     if _h3_ok(Wpe):
-        _gemm_h3(src.view(geo.M, 32 * ldsrc), Wpe, D, out=tok, bias=P[n["pe_b"]], res=pos, row_map=geo.sub2tok)
+        _gemm_h3(src.view(geo.S, 32 * ldsrc), Wpe, D, out=tok, bias=P[n["pe_b"]], res=pos, row_map=geo.sub2tok)
     else:
-        K.gemm(src.view(geo.M, 32 * ldsrc), Wpe, tok, geo.M, D, 32 * ldsrc, 32 * ldsrc, 32 * ldsrc, D,
+        K.gemm(src.view(geo.S, 32 * ldsrc), Wpe, tok, geo.S, D, 32 * ldsrc, 32 * ldsrc, 32 * ldsrc, D,
                bias=P[n["pe_b"]], res=pos, ldr=D, row_map=geo.sub2tok)
     sv.update(Wpe=Wpe, src=src, ldsrc=ldsrc)
     # conditioning c = t_embedder(t) + y_embedder(labels) (dit:572-574)
@@ -511,14 +568,20 @@ def regularizer_forward(P, n, x, t, labels, meta):
     Wl, bl = P[n["fl_w"]], P[n["fl_b"]]
     Cout = Wl.shape[0] // 32
     if resid:
-        # r = relu(DiT(res) + res): the final ConvBlock's ReLU (dit:1344) after the residual
+        # r = relu(DiT(res) + res): the final ConvBlock's ReLU (dit:1344) after the residual.  With a
+        # crop shift the Linear scatters z alone and box_shift adds res and applies the ReLU
+        # (zeros on slack rows); without one the GEMM does, and the slack rows are cleared for the conv.
         r = _empty((geo.V, D), dev)
+        fuse = {} if geo.shifted else dict(res=res.view(geo.S, 32 * D), act=7)
         if _h3_ok(Wl):
-            _gemm_h3(hf, Wl, 32 * D, out=r.view(geo.M, 32 * D), bias=bl, res=res.view(geo.M, 32 * D),
-                     row_map=geo.tok2sub, act=7)
+            _gemm_h3(hf, Wl, 32 * D, out=r.view(geo.S, 32 * D), bias=bl, row_map=geo.tok2sub, **fuse)
         else:
-            K.gemm(hf, Wl, r.view(geo.M, 32 * D), geo.M, 32 * D, D, D, D, 32 * D, bias=bl,
-                   res=res.view(geo.M, 32 * D), ldr=32 * D, row_map=geo.tok2sub, act=7)
+            K.gemm(hf, Wl, r.view(geo.S, 32 * D), geo.M, 32 * D, D, D, D, 32 * D, bias=bl,
+                   ldr=32 * D if fuse else 0, row_map=geo.tok2sub, **fuse)
+        if geo.shifted:
+            r = K.box_shift(r, D, grid, geo.box, geo.shift, res=res, relu=True)
+        else:
+            _zero(r, D, geo)
         # final conv D -> cin (dit:1302): P = r Wf2^T, then the 27-tap gather-sum
         Wf2 = K.permute(P[n["fin_w"]], (27, cin, D), (1, D * 27, 27)).view(27 * cin, D)
         if _thin_h3(D):
@@ -530,18 +593,20 @@ def regularizer_forward(P, n, x, t, labels, meta):
         sv.update(r=r, Wf2=Wf2)
         from . import engine
         if engine.CAPTURE is not None:                     # test hook: the final ConvBlock's ReLU decisions
-            engine.CAPTURE.append(dict(relu_inputs=[r], grid=grid, C=D))
+            engine.CAPTURE.append(dict(relu_inputs=[r], grid=grid, C=D, **(dict(box=geo.box) if geo.slack else {})))
     else:
         # DiTNet: the Linear's (p, q, r, c) outputs straight into the thin blocked volume
         Wlp, blp = _padded_final_linear(Wl, bl, Cout)
         o = _empty((geo.V, PAD_CIN), dev)
         if _h3_ok(Wlp):
-            _gemm_h3(hf, Wlp, 32 * PAD_CIN, out=o.view(geo.M, 32 * PAD_CIN), bias=blp, row_map=geo.tok2sub)
+            _gemm_h3(hf, Wlp, 32 * PAD_CIN, out=o.view(geo.S, 32 * PAD_CIN), bias=blp, row_map=geo.tok2sub)
         else:
-            K.gemm(hf, Wlp, o.view(geo.M, 32 * PAD_CIN), geo.M, 32 * PAD_CIN, D, D, D, 32 * PAD_CIN, bias=blp,
+            K.gemm(hf, Wlp, o.view(geo.S, 32 * PAD_CIN), geo.M, 32 * PAD_CIN, D, D, D, 32 * PAD_CIN, bias=blp,
                    row_map=geo.tok2sub)
+        if geo.shifted:                                    # unpatchify2's centre crop (dit:539-541)
+            o = K.box_shift(o, PAD_CIN, grid, geo.box, geo.shift)
         sv.update(Wlp=Wlp, cout=Cout)
-    out = K.swin_post(o, (B, E, T, Y, X), pad)
+    out = _post(o, (B, E, T, Y, X), pad, geo)
     return out, sv
 
 
@@ -554,7 +619,7 @@ def regularizer_backward(P, n, sv, gout, meta, G):
     D = P[n["pe_w"]].shape[0]
     hd = D // heads
     cin = 2 * E
-    go = K.swin_post_bwd(gout.contiguous(), torch.float32, pad, PAD_CIN)       # [V, 8]
+    go = _post_bwd(gout.contiguous(), pad, geo)                                # [V, 8], zero on slack rows
     Wl = P[n["fl_w"]]
     if resid:
         # final conv: o = col2im(+1)(r Wf2^T) + b
@@ -567,9 +632,11 @@ def regularizer_backward(P, n, sv, gout, meta, G):
             ds = _gemm_h3(G2c, sv["Wf2"], D, trans=True, act=6, aux=sv["r"])
         else:
             ds = K.linear_dx(G2c, sv["Wf2"], act=6, aux=sv["r"])
-        dsub = ds.view(geo.M, 32 * D)
+        # ds is zero on slack rows (r is); the crop's adjoint puts it back where the Linear wrote
+        dsub = (K.box_shift(ds, D, grid, geo.box, geo.shift, transpose=True) if geo.shifted else ds).view(geo.S, 32 * D)
     else:
-        dsub = go.view(geo.M, 32 * PAD_CIN)
+        dsub = (K.box_shift(go, PAD_CIN, grid, geo.box, geo.shift, transpose=True) if geo.shifted else
+                go).view(geo.S, 32 * PAD_CIN)
     # final Linear (row-mapped into subpatches): out[tok2sub[m]] = hf[m] Wl^T + bl (+ res)
     Wg = Wl if resid else sv["Wlp"]
     Cw = Wg.shape[0]
@@ -577,8 +644,8 @@ def regularizer_backward(P, n, sv, gout, meta, G):
     if _h3_ok(Wg, True):
         _gemm_h3(dsub, Wg, D, trans=True, out=dhf, row_map=geo.sub2tok)
     else:
-        K.gemm(dsub, Wg, dhf, geo.M, D, Cw, Cw, D, D, b_trans=1, row_map=geo.sub2tok)
-    hf_sub = K.gather_rows(sv["hf"], geo.sub2tok, geo.M, torch.float32)
+        K.gemm(dsub, Wg, dhf, geo.S, D, Cw, Cw, D, D, b_trans=1, row_map=geo.sub2tok)
+    hf_sub = K.gather_rows(sv["hf"], geo.sub2tok, geo.S, torch.float32)
     if resid:
         _lin_grads(dsub, hf_sub, G[n["fl_w"]], G[n["fl_b"]])
     else:
@@ -607,10 +674,10 @@ def regularizer_backward(P, n, sv, gout, meta, G):
     dth = _vec(1, dts, sv["th"])
     _lin_grads(dth, sv["tf"], G[n["t0_w"]], G[n["t0_b"]])
     # patch embed: tok[sub2tok[j]] = src_sub[j] Wpe^T + b + pos
-    dtok_sub = K.gather_rows(dtok, geo.sub2tok, geo.M, torch.float32)
+    dtok_sub = K.gather_rows(dtok, geo.sub2tok, geo.S, torch.float32)
     K.colsum(dtok, G[n["pe_b"]])
     ldsrc = sv["ldsrc"]
-    src_sub = sv["src"].view(geo.M, 32 * ldsrc)
+    src_sub = sv["src"].view(geo.S, 32 * ldsrc)
     dWpe = _zeros((D, 32 * ldsrc), dev)
     _lin_grads(dtok_sub, src_sub, dWpe, None)
     Cpe = P[n["pe_w"]].shape[1]
@@ -620,10 +687,11 @@ def regularizer_backward(P, n, sv, gout, meta, G):
         # d res = ds (the final residual) + patch-embed dgrad
         dres = _empty((geo.V, D), dev)
         if _h3_ok(sv["Wpe"], True):
-            _gemm_h3(dtok_sub, sv["Wpe"], 32 * D, trans=True, out=dres.view(geo.M, 32 * D), res=ds.view(geo.M, 32 * D))
+            _gemm_h3(dtok_sub, sv["Wpe"], 32 * D, trans=True, out=dres.view(geo.S, 32 * D), res=ds.view(geo.S, 32 * D))
         else:
-            K.gemm(dtok_sub, sv["Wpe"], dres.view(geo.M, 32 * D), geo.M, 32 * D, D, D, 32 * D, 32 * D, b_trans=1,
-                   res=ds.view(geo.M, 32 * D), ldr=32 * D)
+            K.gemm(dtok_sub, sv["Wpe"], dres.view(geo.S, 32 * D), geo.S, 32 * D, D, D, 32 * D, 32 * D, b_trans=1,
+                   res=ds.view(geo.S, 32 * D), ldr=32 * D)
+        _zero(dres, D, geo)               # the gradient of the embed's zero pad: not the SFE conv's
         # SFE: res = col Wsfe^T + b
         tld = sv["col"].shape[1]
         dWs = _zeros((D, tld), dev)
@@ -637,11 +705,11 @@ def regularizer_backward(P, n, sv, gout, meta, G):
     else:
         du = _empty((geo.V, PAD_CIN), dev)
         if _h3_ok(sv["Wpe"], True):
-            _gemm_h3(dtok_sub, sv["Wpe"], 32 * PAD_CIN, trans=True, out=du.view(geo.M, 32 * PAD_CIN))
+            _gemm_h3(dtok_sub, sv["Wpe"], 32 * PAD_CIN, trans=True, out=du.view(geo.S, 32 * PAD_CIN))
         else:
-            K.gemm(dtok_sub, sv["Wpe"], du.view(geo.M, 32 * PAD_CIN), geo.M, 32 * PAD_CIN, D, D, 32 * PAD_CIN,
+            K.gemm(dtok_sub, sv["Wpe"], du.view(geo.S, 32 * PAD_CIN), geo.S, 32 * PAD_CIN, D, D, 32 * PAD_CIN,
                    32 * PAD_CIN, b_trans=1)
-    return K.swin_pre_bwd(du, (B, E, T, Y, X), pad)
+    return _pre_bwd(du, (B, E, T, Y, X), pad, geo)
 
 
 class _DiTFn(torch.autograd.Function):

@@ -3,7 +3,8 @@ one autograd node per network call, on the DiT engine's kernels and helpers
 (dl_cs.models.dit_engine: adaLN LayerNorm, flash MHSA, gated Linears, the fp8
 token-Linear path).
 
-Layouts (fp32; B samples, time padded to F = T + 2 pad frames, Y, X multiples of 4):
+Layouts (fp32; B samples, time padded to F = T + 2 pad frames; any F, Y, X -- a grid that is
+no multiple of 4 runs in the grid rounded up, see LGeo and dit_engine's "Any grid size"):
   * the 2E-channel volume in the patch-blocked channels-last layout of the Swin
     path (row(b,t,y,x) = patch-of-4x4x4 * 64 + (t%4) 16 + (y%4) 4 + x%4): a 2-D
     (4, 4) patch of one frame (lat:89-147) is 16 consecutive rows, so the patch
@@ -19,35 +20,53 @@ Gated residual branches g * (x W^T + b) (lat:313-314) run as one GEMM on
 gate-scaled weights; adaLN-modulated LayerNorms (lat:33-34) are dlcs_layernorm
 with gamma = 1 + scale, beta = shift; the frame table (lat:532-535) is added to
 every token before the first temporal block (frozen: no gradient).
+
+Any grid size: the per-frame patch embed zero-pads the end of Y and X up to the (4, 4)
+patch (lat:126-129, :193-214) and unpatchify2 crops the centre (lat:450-475).  The tokens
+are the reference's F frames x ceil(Y/4) x ceil(X/4) patches (LGeo.sub2tok skips the frames
+F .. Dp-1 of the rounded-up grid), and the crop is dlcs_box_shift with no time shift.
 """
 import numpy as np
 import torch
 
 from .. import _lib
 from . import _ops as K
-from .dit_engine import (PAD_CIN, _dev_i32, _dx, _empty, _gated_grad, _gated_pack, _gemm_h3, _h3_ok, _lin,
-                         _lin_grads, _ln, _mhsa, _mhsa_bwd, _packs, _scale_rows, _vec, _zeros)
+from .dit_engine import (PAD_CIN, _ceil_div, _dev_i32, _dx, _empty, _gated_grad, _gated_pack, _gemm_h3, _h3_ok, _lin,
+                         _lin_grads, _ln, _mhsa, _mhsa_bwd, _packs, _post, _post_bwd, _pre, _pre_bwd, _scale_rows,
+                         _vec, _zeros)
 
 _GEO = {}
 
 
 class LGeo:
-    """Index maps of one (B, F, Y, X) Latte geometry (host-built once, cached)."""
+    """Index maps of one (B, F, Y, X) Latte geometry (host-built once, cached).
+
+    The box (B, F, Y, X) sits at the origin of the layout grid `grid`, each axis rounded up
+    to 4 (V rows, S = V / 16 per-frame patches); the tokens are the reference's F frames of
+    Hp x Wp = ceil(Y/4) x ceil(X/4) patches (lat:193-214).  sub2tok is -1 on the patches of
+    the frames F .. Dp-1; `shift` is where unpatchify2's centre crop starts (lat:450-475)."""
 
     def __init__(self, B, F, Y, X, device):
         self.B, self.F, self.Y, self.X = B, F, Y, X
-        self.Hp, self.Wp = Y // 4, X // 4
+        self.box = (B, F, Y, X)
+        self.grid = (B, K.pad4(F), K.pad4(Y), K.pad4(X))
+        self.slack = self.grid != self.box
+        self.Hp, self.Wp = _ceil_div(Y, 4), _ceil_div(X, 4)
+        self.shift = (0, _ceil_div(4 * self.Hp - Y, 2), _ceil_div(4 * self.Wp - X, 2))
+        self.shifted = any(self.shift)
         self.Np = self.Hp * self.Wp
-        self.V = B * F * Y * X
+        self.V = B * self.grid[1] * self.grid[2] * self.grid[3]
+        self.S = self.V // 16
         self.M = B * F * self.Np
         self.Mb = self.M // B
         Hp, Wp, Np = self.Hp, self.Wp, self.Np
         b, f, h, w = np.meshgrid(np.arange(B), np.arange(F), np.arange(Hp), np.arange(Wp), indexing="ij")
         tok = (b * F + f) * Np + h * Wp + w                              # (b, f, p) token order
-        sub = (((b * (F // 4) + f // 4) * Hp + h) * Wp + w) * 4 + f % 4   # 16-row 2-D patch of the blocked layout
+        nT = self.grid[1] // 4
+        sub = (((b * nT + f // 4) * Hp + h) * Wp + w) * 4 + f % 4         # 16-row 2-D patch of the blocked layout
         tim = (b * Np + h * Wp + w) * F + f                              # (b, p, f): temporal sequences
         tok, sub, tim, f = tok.reshape(-1), sub.reshape(-1), tim.reshape(-1), f.reshape(-1)
-        sub2tok = np.empty(self.M, np.int64)
+        sub2tok = np.full(self.S, -1, np.int64)
         sub2tok[sub] = tok
         tok2sub = np.empty(self.M, np.int64)
         tok2sub[tok] = sub
@@ -228,8 +247,6 @@ def network_forward(P, n, x, t, meta):
     B, E, T, Y, X = x.shape
     pad, depth, heads = meta["pad"], meta["depth"], meta["heads"]
     F = T + 2 * pad
-    if F % 4 or Y % 4 or X % 4:
-        raise NotImplementedError("dl_cs HIP Latte: T + 2 pad, Y and X must be multiples of 4")
     dev = x.device
     geo = LGeo.get(B, F, Y, X, dev)
     cin = 2 * E
@@ -239,15 +256,15 @@ def network_forward(P, n, x, t, meta):
         raise NotImplementedError(f"dl_cs HIP Latte: head dim {D}/{heads} must be <= 32 and a multiple of 4")
     if F > P[n["temp"]].shape[1]:
         raise ValueError(f"{F} frames exceed the TempEmbed table ({P[n['temp']].shape[1]})")
-    u = K.swin_pre(x.contiguous(), torch.float32, pad, PAD_CIN)                 # [V, 8]  (lat:882-894)
+    u = _pre(x.contiguous(), pad, geo)                        # [V, 8]  (lat:882-894), zero on slack rows
     Wpe, Wlp, blp = _patch_weights(P, n, D, cin)
     # patch embed + position table (lat:513-516), token order via the row map
     pos = K.gather_rows(P[n["pos"]].view(-1, D), meta["pos_index"](geo), geo.M, torch.float32)
     tok = _empty((geo.M, D), dev)
     if _h3_ok(Wpe):
-        _gemm_h3(u.view(geo.M, 16 * PAD_CIN), Wpe, D, out=tok, bias=P[n["pe_b"]], res=pos, row_map=geo.sub2tok)
+        _gemm_h3(u.view(geo.S, 16 * PAD_CIN), Wpe, D, out=tok, bias=P[n["pe_b"]], res=pos, row_map=geo.sub2tok)
     else:
-        K.gemm(u.view(geo.M, 16 * PAD_CIN), Wpe, tok, geo.M, D, 16 * PAD_CIN, 16 * PAD_CIN, 16 * PAD_CIN, D,
+        K.gemm(u.view(geo.S, 16 * PAD_CIN), Wpe, tok, geo.S, D, 16 * PAD_CIN, 16 * PAD_CIN, 16 * PAD_CIN, D,
                bias=P[n["pe_b"]], res=pos, ldr=D, row_map=geo.sub2tok)
     # conditioning c = t_embedder(t) (lat:521-523; extras = 1: no label / text term)
     tf = _empty((B, 256), dev)
@@ -274,11 +291,13 @@ def network_forward(P, n, x, t, meta):
         hf[rs], mf[rs], rf[rs] = _ln(tok[rs], gam_f[b], sh_f[b], geo.Mb)
     o = _empty((geo.V, PAD_CIN), dev)
     if _h3_ok(Wlp):
-        _gemm_h3(hf, Wlp, 16 * PAD_CIN, out=o.view(geo.M, 16 * PAD_CIN), bias=blp, row_map=geo.tok2sub)
+        _gemm_h3(hf, Wlp, 16 * PAD_CIN, out=o.view(geo.S, 16 * PAD_CIN), bias=blp, row_map=geo.tok2sub)
     else:
-        K.gemm(hf, Wlp, o.view(geo.M, 16 * PAD_CIN), geo.M, 16 * PAD_CIN, D, D, D, 16 * PAD_CIN, bias=blp,
+        K.gemm(hf, Wlp, o.view(geo.S, 16 * PAD_CIN), geo.M, 16 * PAD_CIN, D, D, D, 16 * PAD_CIN, bias=blp,
                row_map=geo.tok2sub)
-    out = K.swin_post(o, (B, E, T, Y, X), pad)                                 # lat:896-907
+    if geo.shifted:                                            # unpatchify2's centre crop (lat:450-475)
+        o = K.box_shift(o, PAD_CIN, geo.grid, geo.box, geo.shift)
+    out = _post(o, (B, E, T, Y, X), pad, geo)                                  # lat:896-907
     sv = dict(u=u, geo=geo, shape=(B, E, T, Y, X), Wpe=Wpe, Wlp=Wlp, tf=tf, th=th, ts=ts, c=c, sc=scv,
               blocks=svb, tok_last=tok, gam_f=gam_f, hf=hf, mf=mf, rf=rf)
     return out, sv
@@ -292,8 +311,10 @@ def network_backward(P, n, sv, gout, meta, G):
     D = P[n["pe_w"]].shape[0]
     hd = D // heads
     cin = 2 * E
-    go = K.swin_post_bwd(gout.contiguous(), torch.float32, pad, PAD_CIN)       # [V, 8]
-    dsub = go.view(geo.M, 16 * PAD_CIN)
+    go = _post_bwd(gout.contiguous(), pad, geo)                                # [V, 8], zero on slack rows
+    if geo.shifted:                                            # the crop's adjoint
+        go = K.box_shift(go, PAD_CIN, geo.grid, geo.box, geo.shift, transpose=True)
+    dsub = go.view(geo.S, 16 * PAD_CIN)
     # final Linear (row-mapped into the 2-D patches): o[tok2sub[m]] = hf[m] Wlp^T + blp
     Wlp = sv["Wlp"]
     Cw = Wlp.shape[0]
@@ -301,8 +322,8 @@ def network_backward(P, n, sv, gout, meta, G):
     if _h3_ok(Wlp, True):
         _gemm_h3(dsub, Wlp, D, trans=True, out=dhf, row_map=geo.sub2tok)
     else:
-        K.gemm(dsub, Wlp, dhf, geo.M, D, Cw, Cw, D, D, b_trans=1, row_map=geo.sub2tok)
-    hf_sub = K.gather_rows(sv["hf"], geo.sub2tok, geo.M, torch.float32)
+        K.gemm(dsub, Wlp, dhf, geo.S, D, Cw, Cw, D, D, b_trans=1, row_map=geo.sub2tok)
+    hf_sub = K.gather_rows(sv["hf"], geo.sub2tok, geo.S, torch.float32)
     dWp_, dbp_ = _zeros((Cw, D), dev), _zeros((Cw,), dev)
     _lin_grads(dsub, hf_sub, dWp_, dbp_)
     G[n["fl_w"]].view(16, cin, D).add_(dWp_.view(16, PAD_CIN, D)[:, :cin])
@@ -325,19 +346,19 @@ def network_backward(P, n, sv, gout, meta, G):
     dth = _vec(1, dts, sv["th"])
     _lin_grads(dth, sv["tf"], G[n["t0_w"]], G[n["t0_b"]])
     # patch embed: tok[sub2tok[j]] = u_patch[j] Wpe^T + b + pos
-    dtok_sub = K.gather_rows(dtok, geo.sub2tok, geo.M, torch.float32)
+    dtok_sub = K.gather_rows(dtok, geo.sub2tok, geo.S, torch.float32)
     K.colsum(dtok, G[n["pe_b"]])
     dWpe = _zeros((D, 16 * PAD_CIN), dev)
-    _lin_grads(dtok_sub, sv["u"].view(geo.M, 16 * PAD_CIN), dWpe, None)
+    _lin_grads(dtok_sub, sv["u"].view(geo.S, 16 * PAD_CIN), dWpe, None)
     K.permute(dWpe.view(D, 16, PAD_CIN)[:, :, :cin].contiguous(), (D, cin, 16), (16 * cin, 1, cin),
               out=G[n["pe_w"]].view(D, cin, 16), accumulate=1)
     du = _empty((geo.V, PAD_CIN), dev)
     if _h3_ok(sv["Wpe"], True):
-        _gemm_h3(dtok_sub, sv["Wpe"], 16 * PAD_CIN, trans=True, out=du.view(geo.M, 16 * PAD_CIN))
+        _gemm_h3(dtok_sub, sv["Wpe"], 16 * PAD_CIN, trans=True, out=du.view(geo.S, 16 * PAD_CIN))
     else:
-        K.gemm(dtok_sub, sv["Wpe"], du.view(geo.M, 16 * PAD_CIN), geo.M, 16 * PAD_CIN, D, D, 16 * PAD_CIN,
+        K.gemm(dtok_sub, sv["Wpe"], du.view(geo.S, 16 * PAD_CIN), geo.S, 16 * PAD_CIN, D, D, 16 * PAD_CIN,
                16 * PAD_CIN, b_trans=1)
-    return K.swin_pre_bwd(du, (B, E, T, Y, X), pad)
+    return _pre_bwd(du, (B, E, T, Y, X), pad, geo)
 
 
 class _LatteFn(torch.autograd.Function):

@@ -540,7 +540,8 @@ int dlcs_swin_post_bwd(int dtype, const void* gout, void* go, int64_t B, int64_t
                        int64_t pad, int64_t ldc, dlcs_stream_t stream);
 
 /* ---- A box inside a padded grid (box.hip) --------------------------------------------
- * What lets the ResNet, SE and CBAM regularisers take any grid.  The conv, SE and CBAM
+ * What lets the ResNet, SE and CBAM regularisers (and, with box_shift, the DiT / Latte
+ * denoisers) take any grid.  The conv, SE and CBAM
  * entry points keep requiring D, H, W multiples of 4; a true grid ("box") (B, D, H, W)
  * sits at the origin of a padded grid (B, Dp, Hp, Wp), Dp >= D, Hp >= H, Wp >= W
  * multiples of 4, whose patch-blocked rows those entry points receive.  Rows whose
@@ -558,6 +559,21 @@ int dlcs_swin_post_bwd(int dtype, const void* gout, void* go, int64_t B, int64_t
  *     nothing, writes nothing to rows of the box or to columns [C, ld); work and bytes
  *     are proportional to the slack rows.  16-B stores when C % 4 == 0, ld % 4 == 0 and
  *     x is 16-B aligned, else one float at a time.  No slack: no launch, returns 0.
+ *   box_shift: a voxel shift (sd, sh, sw) >= 0 of the box inside the padded grid, the centre
+ *     crop of the DiT / Latte unpatchify2 (dit:539-541, lat:450-475) whose result the final
+ *     Linear has scattered at the origin.  src [B Dp Hp Wp, ld_src], dst [.., ld_dst] and the
+ *     optional residual [.., ld_res] are rows of the same padded grid; dst must not be src.
+ *       transpose = 0: dst[row(b,t,y,x)][0:C) = src[row(b,t+sd,y+sh,x+sw)][0:C)
+ *         (+ residual[row(b,t,y,x)][0:C), then max(., 0) when relu) for every voxel of the
+ *         box; +0.0 into [0, C) of every slack row.
+ *       transpose = 1 (the adjoint; no residual, no relu): dst[row(b,t',y',x')][0:C) =
+ *         src[row(b,t'-sd,y'-sh,x'-sw)][0:C) where that source is a voxel of the box, +0.0
+ *         on every other row of the padded grid.
+ *     Both are gathers: every dst row is written exactly once, no atomics, columns
+ *     [C, ld_dst) untouched.  16-B accesses when C % 4 == 0, every ld % 4 == 0 and every
+ *     pointer is 16-B aligned, else one float at a time.  D + sd > Dp, H + sh > Hp or
+ *     W + sw > Wp (the shifted box leaves the padded grid), B or C > 2^20, an ld >= 2^30:
+ *     DLCS_ERR_UNSUPPORTED_SIZE.
  *
  * Padded sizes not multiples of 4, a box larger than the padded grid, or (box_zero)
  * B > 65535: DLCS_ERR_UNSUPPORTED_SIZE and nothing is written.                         */
@@ -571,6 +587,9 @@ int dlcs_box_post_bwd(const void* gout, float* go, int64_t B, int64_t E, int64_t
                       int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
 int dlcs_box_zero(float* x, int64_t ld, int64_t C, int64_t B, int64_t Dp, int64_t Hp, int64_t Wp, int64_t D, int64_t H,
                   int64_t W, dlcs_stream_t stream);
+int dlcs_box_shift(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int64_t C, int64_t B, int64_t Dp,
+                   int64_t Hp, int64_t Wp, int64_t D, int64_t H, int64_t W, int64_t sd, int64_t sh, int64_t sw,
+                   int transpose, const float* residual, int64_t ld_res, int relu, dlcs_stream_t stream);
 int dlcs_box_pre_bf16(const void* x, void* u, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X, int64_t pad,
                       int64_t Dp, int64_t Hp, int64_t Wp, int64_t ldc, dlcs_stream_t stream);
 int dlcs_box_post_bwd_bf16(const void* gout, void* go, int64_t B, int64_t E, int64_t T, int64_t Y, int64_t X,
