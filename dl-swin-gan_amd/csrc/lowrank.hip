@@ -26,6 +26,8 @@
 // R (and in compose the L rows) are staged in LDS with 16-B global reads when r is even
 // and the pointer is 16-B aligned; the block-side stores of extract / project_* and the
 // block reads of combine are 16 B under the same condition on T / r.
+#include <type_traits>
+
 #include "dlcs_common.h"
 
 namespace {
@@ -329,6 +331,230 @@ __global__ void __launch_bounds__(kThreads) lr_compose_kernel(const float2* L, c
     }
 }
 
+// ------------------------------------------------------------------ decompose: one block SVD per workgroup
+// Hestenes one-sided Jacobi on the T columns of the block matrix B [M = E b^2, T], held
+// column-major in LDS (sB[t M + p]) beside V [T, T] (sV[k T + t], the identity at the
+// start).  A step of the round-robin tournament has T / 2 disjoint column pairs; pair k is
+// rotated by the 16 lanes of group k = threadIdx.x / 16 (one DPP row): lane l holds rows
+// l, l + 16, ... (M / 16 of them, a template parameter: 8-B LDS accesses, the rows kept in
+// registers), the four sums alpha, beta, Re gamma, Im gamma are reduced inside the row in a
+// fixed order, and every lane of the group computes the same c, s, phi and rotates its rows
+// of both columns (and of V) in place.  The host launches at least 16 (T + 1) / 2 threads, so
+// a step is one pass; a barrier separates the steps.
+constexpr int kSvdMaxSweeps = 30;
+constexpr float kSvdTol = 1.1920928955078125e-7f;          // 2^-23: |gamma| <= tol sqrt(alpha beta) is orthogonal
+constexpr float kSvdNull = 9.094947017729282e-13f;         // 2^-40 of the largest initial squared column norm
+
+// sum over the 16 lanes of a DPP row (quad_perm xor 1, xor 2, row_half_mirror, row_mirror):
+// every step adds two partial sums of disjoint halves, so all 16 lanes end with the same
+// bits.  All 16 lanes of the row must be active (the callers keep a group's control flow uniform).
+DLCS_DEV float row16_sum(float v) {
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
+}
+
+// squared norm of a column of n rows (n = 0: an idle group, which still takes part in the reduction)
+DLCS_DEV float col_norm2(const float2* col, int n, int lane) {
+    float a = 0.0f;
+    for (int i = lane; i < n; i += 16) {
+        const float2 v = col[i];
+        a = fmaf(v.x, v.x, a); a = fmaf(v.y, v.y, a);
+    }
+    return row16_sum(a);
+}
+
+// a_p <- c a_p - conj(m) a_q,  a_q <- m a_p + c a_q  (m = s phi)
+DLCS_DEV void rotate2(float2& a, float2& b, float c, float2 m) {
+    float2 na, nb;
+    na.x = fmaf(c, a.x, -fmaf(m.x, b.x, m.y * b.y));
+    na.y = fmaf(c, a.y, -fmaf(m.x, b.y, -m.y * b.x));
+    nb.x = fmaf(c, b.x, fmaf(m.x, a.x, -m.y * a.y));
+    nb.y = fmaf(c, b.y, fmaf(m.x, a.y, m.y * a.x));
+    a = na; b = nb;
+}
+
+// One column pair by one 16-lane group: lane l holds rows l + 16 (k ^ k0), k < NIT = M / 16, of
+// both columns in registers between the sums and the rotation, so a step reads and writes
+// each row once and all its LDS reads are in flight together.  k0 = 1 in odd groups starts
+// them 16 rows (32 banks) down, so that the two groups of a 32-lane half use other banks.
+// An idle group (act false) adds zeros and still takes part in the reductions.  Returns
+// whether the pair was rotated (the same in all 16 lanes).
+template <int NIT>
+DLCS_DEV bool svd_pair(float2* cp, float2* cq, float2* vp, float2* vq, int T, bool act, int lane, int k0, float thr) {
+    float2 a[NIT], b[NIT];
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+        a[k] = b[k] = make_float2(0.0f, 0.0f);
+        if (act) { a[k] = cp[lane + 16 * (k ^ k0)]; b[k] = cq[lane + 16 * (k ^ k0)]; }
+    }
+    float al = 0.0f, be = 0.0f, gr = 0.0f, gi = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+        al = fmaf(a[k].x, a[k].x, al); al = fmaf(a[k].y, a[k].y, al);
+        be = fmaf(b[k].x, b[k].x, be); be = fmaf(b[k].y, b[k].y, be);
+        gr = fmaf(a[k].x, b[k].x, gr); gr = fmaf(a[k].y, b[k].y, gr);      // gamma = a_p^H a_q
+        gi = fmaf(a[k].x, b[k].y, gi); gi = fmaf(-a[k].y, b[k].x, gi);
+    }
+    al = row16_sum(al); be = row16_sum(be); gr = row16_sum(gr); gi = row16_sum(gi);
+    const float absg = sqrtf(fmaf(gr, gr, gi * gi));
+    if (!(act && al > thr && be > thr && absg > kSvdTol * (sqrtf(al) * sqrtf(be)))) return false;
+    const float z = (be - al) / (2.0f * absg);
+    const float t = (z >= 0.0f ? 1.0f : -1.0f) / (fabsf(z) + sqrtf(fmaf(z, z, 1.0f)));
+    const float c = 1.0f / sqrtf(fmaf(t, t, 1.0f));
+    const float s = c * t;
+    const float2 m = make_float2(s * (gr / absg), s * (gi / absg));
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+        rotate2(a[k], b[k], c, m);
+        cp[lane + 16 * (k ^ k0)] = a[k]; cq[lane + 16 * (k ^ k0)] = b[k];
+    }
+    for (int i = lane; i < T; i += 16) {                   // the same rotation on V's columns
+        float2 x = vp[i], y = vq[i];
+        rotate2(x, y, c, m);
+        vp[i] = x; vq[i] = y;
+    }
+    return true;
+}
+
+template <int NIT>
+__global__ void __launch_bounds__(kThreads) lr_decompose_kernel(const float2* img, const float* win, float2* L,
+                                                                float2* R, float* S, int* info, LrGeo g, int r) {
+    extern __shared__ float2 svd_smem[];                   // sB [T][M], then sV [T][T]
+    __shared__ float swin[16];
+    __shared__ float s_n2[kMaxT];                          // squared column norms
+    __shared__ int s_order[kMaxR], s_null[kMaxR];          // output component j: its column, sigma^2 null
+    __shared__ float2 s_sl[kMaxR], s_sr[kMaxR];            // phase / sqrt(sigma), phase sqrt(sigma)
+    __shared__ int s_rot;                                  // a pair of this sweep was rotated
+    const int T = g.T, M = 16 * NIT;                       // M = E b^2, a multiple of 16
+    float2* sB = svd_smem;
+    float2* sV = svd_smem + T * M;
+    const int n = blockIdx.x, nthr = blockDim.x;
+    const int lane = threadIdx.x & 15, grp = threadIdx.x >> 4, ngrp = nthr >> 4;
+
+    // ---- stage the block as lr_extract_kernel does (x-runs; divide 0), V = identity
+    if (threadIdx.x < g.b) swin[threadIdx.x] = win[threadIdx.x];
+    __syncthreads();
+    {
+        const int by = n / g.nbx, bx = n % g.nbx, bb = g.b * g.b;
+        for (int i = threadIdx.x; i < M * T; i += nthr) {
+            const int p = i % M, t = i / M;
+            const int e = p / bb, q = p - e * bb;
+            const int iy = q / g.b, ix = q - iy * g.b;
+            const int y = by * g.s + iy - g.py0, x = bx * g.s + ix - g.px0;
+            float2 v = make_float2(0.0f, 0.0f);
+            if (y >= 0 && y < g.Y && x >= 0 && x < g.X) {
+                v = img[(((long)e * T + t) * g.Y + y) * g.X + x];
+                const float w = swin[iy] * swin[ix];
+                v.x *= w; v.y *= w;
+            }
+            sB[t * M + p] = v;
+        }
+        for (int i = threadIdx.x; i < T * T; i += nthr) sV[i] = make_float2(i / T == i % T ? 1.0f : 0.0f, 0.0f);
+    }
+    __syncthreads();
+
+    // ---- the null threshold from the initial column norms
+    for (int t0 = 0; t0 < T; t0 += ngrp) {
+        const int t = t0 + grp;
+        const float n2 = col_norm2(sB + (t < T ? t : 0) * M, t < T ? M : 0, lane);
+        if (t < T && lane == 0) s_n2[t] = n2;
+    }
+    __syncthreads();
+    float thr = 0.0f;
+    for (int t = 0; t < T; ++t) thr = fmaxf(thr, s_n2[t]);
+    thr *= kSvdNull;
+
+    // ---- sweeps: np - 1 steps over np = T rounded up to even players; an index >= T is the bye
+    const int np = (T + 1) & ~1, half = np >> 1;
+    int sweeps = 0;
+    while (sweeps < kSvdMaxSweeps) {
+        if (threadIdx.x == 0) s_rot = 0;
+        __syncthreads();
+        for (int step = 0; step < np - 1; ++step) {
+            int p = 0, q = 0;
+            bool act = grp < half;
+            if (act) {                                     // circle method: player np - 1 stays, the rest turn
+                const int a = grp == 0 ? np - 1 : (step + grp) % (np - 1);
+                const int c = grp == 0 ? step : (step - grp + np - 1) % (np - 1);
+                p = a < c ? a : c; q = a < c ? c : a;
+                act = q < T;
+            }
+            const int k0 = (NIT > 1 && (grp & 1)) ? 1 : 0;
+            if (svd_pair<NIT>(sB + p * M, sB + q * M, sV + p * T, sV + q * T, T, act, lane, k0, thr) && lane == 0)
+                s_rot = 1;
+            __syncthreads();
+        }
+        ++sweeps;
+        const int rotated = s_rot;
+        __syncthreads();                                   // all have read s_rot before it is cleared
+        if (!rotated) break;
+    }
+
+    // ---- order the columns by sigma^2 descending (ties: the lower column first), phases, scales
+    for (int t0 = 0; t0 < T; t0 += ngrp) {
+        const int t = t0 + grp;
+        const float n2 = col_norm2(sB + (t < T ? t : 0) * M, t < T ? M : 0, lane);
+        if (t < T && lane == 0) s_n2[t] = n2;
+    }
+    if (threadIdx.x < r) s_order[threadIdx.x] = threadIdx.x;       // NaN norms rank nothing: keep the indices valid
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += nthr) {
+        const float v = s_n2[t];
+        int rank = 0;
+        for (int j = 0; j < T; ++j) { const float u = s_n2[j]; rank += (u > v || (u == v && j < t)) ? 1 : 0; }
+        if (rank < r) s_order[rank] = t;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < r; j += nthr) {
+        const int k = s_order[j];
+        const float s2 = s_n2[k];
+        const float sig = sqrtf(s2), rs = sqrtf(sig);
+        // the unit phase that makes the largest entry of v_k real and positive (the lowest t on a tie)
+        float best = -1.0f;
+        float2 vb = make_float2(1.0f, 0.0f);
+        for (int t = 0; t < T; ++t) {
+            const float2 v = sV[k * T + t];
+            const float m2 = fmaf(v.x, v.x, v.y * v.y);
+            if (m2 > best) { best = m2; vb = v; }
+        }
+        const float mag = sqrtf(best);
+        const float2 ph = mag > 0.0f ? make_float2(vb.x / mag, -vb.y / mag) : make_float2(1.0f, 0.0f);
+        const int null = !(s2 > thr);
+        s_null[j] = null;
+        s_sl[j] = null ? make_float2(0.0f, 0.0f) : make_float2(ph.x / rs, ph.y / rs);
+        s_sr[j] = make_float2(ph.x * rs, ph.y * rs);
+        if (S) S[(long)n * r + j] = sig;
+    }
+    if (info && threadIdx.x == 0) info[n] = sweeps;
+    __syncthreads();
+
+    // ---- L[n, p, j] = a_k[p] phase / sqrt(sigma),  R[n, t, j] = v_k[t] phase sqrt(sigma);  0 for a null sigma^2
+    float2* Ln = L + (long)n * M * r;
+    for (int i = threadIdx.x; i < M * r; i += nthr) {
+        const int p = i / r, j = i - p * r;
+        float2 o = make_float2(0.0f, 0.0f);
+        if (!s_null[j]) {
+            const float2 a = sB[s_order[j] * M + p], sc = s_sl[j];
+            o.x = fmaf(a.x, sc.x, -a.y * sc.y);
+            o.y = fmaf(a.x, sc.y, a.y * sc.x);
+        }
+        Ln[i] = o;
+    }
+    float2* Rn = R + (long)n * T * r;
+    for (int i = threadIdx.x; i < T * r; i += nthr) {
+        const int t = i / r, j = i - t * r;
+        float2 o = make_float2(0.0f, 0.0f);
+        if (!s_null[j]) {
+            const float2 a = sV[s_order[j] * T + t], sc = s_sr[j];
+            o.x = fmaf(a.x, sc.x, -a.y * sc.y);
+            o.y = fmaf(a.x, sc.y, a.y * sc.x);
+        }
+        Rn[i] = o;
+    }
+}
+
 // geometry of lowrank:47-77; false outside the supported range
 bool lr_geo(int64_t E, int64_t T, int64_t Y, int64_t X, int64_t b, LrGeo* g) {
     if (!(b == 4 || b == 8 || b == 16)) return false;
@@ -408,6 +634,34 @@ int dlcs_lr_project_r(const void* image, const void* L, const float* weights, co
     hipLaunchKernelGGL(lr_project_r_kernel, dim3((unsigned)(g.nby * g.nbx)), dim3(kThreads), 0, (hipStream_t)stream,
                        (const float2*)image, divide ? weights : nullptr, win, (const float2*)L, (float2*)out, g, (int)r,
                        vec_l);
+    return dlcs_launch_status();
+}
+
+int dlcs_lr_decompose(const void* image, const float* win, void* L, void* R, float* S, int32_t* info, int64_t E,
+                      int64_t T, int64_t Y, int64_t X, int64_t b, int64_t r, dlcs_stream_t stream) {
+    LrGeo g;
+    DLCS_CHECK_ARG(image && win && L && R);
+    if (!lr_geo(E, T, Y, X, b, &g) || r < 1 || r > kMaxR || r > T) return DLCS_ERR_UNSUPPORTED_SIZE;
+    // 16 lanes per pair of a step, whole waves: 64 threads up to T = 8, 256 from T = 25
+    const int pairs = (g.T + 1) / 2;
+    const int threads = (16 * pairs + 63) & ~63;
+    const size_t sm = (size_t)g.T * (g.E * g.b * g.b + g.T) * sizeof(float2);   // at most 136 KiB
+    auto launch = [&](auto NIT) {
+        constexpr int nit = decltype(NIT)::value;
+        (void)hipFuncSetAttribute((const void*)lr_decompose_kernel<nit>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)sm);
+        hipLaunchKernelGGL(lr_decompose_kernel<nit>, dim3((unsigned)(g.nby * g.nbx)), dim3(threads), sm,
+                           (hipStream_t)stream, (const float2*)image, win, (float2*)L, (float2*)R, S, (int*)info, g,
+                           (int)r);
+    };
+    switch (g.E * g.b * g.b / 16) {                        // rows per lane: E b^2 / 16
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        case 8: launch(std::integral_constant<int, 8>{}); break;
+        case 16: launch(std::integral_constant<int, 16>{}); break;
+        default: launch(std::integral_constant<int, 32>{}); break;
+    }
     return dlcs_launch_status();
 }
 

@@ -171,6 +171,7 @@ SIGNATURES = {
     "dlcs_lr_compose": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_lr_project_l": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "dlcs_lr_project_r": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "dlcs_lr_decompose": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     # plane conv of the DSLR family's bf16 path (conv2d.hip)
     "dlcs_conv2d_k3": [_P, _I64, _I64, _P, _I64, _P, _P, _INT, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _P, _I64,
                        _P, _INT, _I64, _F, _INT, _P],

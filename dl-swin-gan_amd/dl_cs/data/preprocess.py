@@ -9,7 +9,9 @@ VDkt undersampling, 95th-percentile scaling from the time-averaged image, and
 the sliding-window initial guess (pp:54-180).  With lr_decom=True (the DSLR
 family, pp:166-178) the initial image is also factored into its locally
 low-rank block factors and the tuple is (masked k-space, mask, maps, L_init,
-R_init, initial image, scale, target); the truncated SVD runs on the host.
+R_init, initial image, scale, target); the truncated SVD runs on the host, or with
+lr_svd='device' and a CUDA device in the block SVD kernel (dlcs_lr_decompose), whose
+factors carry the kernel's phase convention (lowrank.Decompose).
 
 With device='cuda' every per-voxel step runs on the GPU through libdlcs_hip --
 dlcs_fft2 (augmentation round trip), dlcs_crop_flip, dlcs_sense_adj (target,
@@ -98,9 +100,12 @@ class CinePreprocess(Preprocess):
     """pp:31-180 -- training-time cine preprocessing (augment, simulate
     undersampling, normalise, sliding-window initial guess)."""
 
-    def __init__(self, config, lr_decom=False, use_seed=False, device=None):
+    def __init__(self, config, lr_decom=False, use_seed=False, device=None, lr_svd='host'):
         super().__init__(config, use_seed)
         self.lr_decom = lr_decom                                            # pp:48-52
+        assert lr_svd in ('host', 'device'), lr_svd
+        self.lr_svd = lr_svd                                                # 'device': dlcs_lr_decompose (a CUDA device)
+        self._decompose = {}                                                # lr_svd='device': one per target shape
         if lr_decom:
             D = config.MODEL.PARAMETERS.DSLR
             self.block_size, self.num_basis, self.overlapping = D.BLOCK_SIZE, D.NUM_BASIS, D.OVERLAPPING
@@ -159,7 +164,15 @@ class CinePreprocess(Preprocess):
             else masked                                                     # pp:160-163
         init_image = A(init, adjoint=True)
         if self.lr_decom:                                                   # pp:166-178
-            decompose = lr.Decompose(self.block_size, self.num_basis, list(target.shape), overlapping=self.overlapping)
+            if self.lr_svd == 'device':                                     # the factors never leave the GPU
+                key = tuple(target.shape)
+                if key not in self._decompose:
+                    self._decompose[key] = lr.Decompose(self.block_size, self.num_basis, list(key),
+                                                        overlapping=self.overlapping, svd='device')
+                decompose = self._decompose[key]
+            else:
+                decompose = lr.Decompose(self.block_size, self.num_basis, list(target.shape),
+                                         overlapping=self.overlapping)
             L_init, R_init = decompose(init_image)
             return masked[0], mask[0], maps[0], L_init, R_init, init_image[0], scale, target[0]
         return masked[0], mask[0], maps[0], init_image[0], scale, target[0]

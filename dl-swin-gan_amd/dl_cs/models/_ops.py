@@ -953,6 +953,23 @@ def lr_project_r(image, L, weights, win, b, divide=False):
     return out
 
 
+def lr_decompose(image, win, b, r, want_s=False, want_info=False):
+    """L [N, E b^2, r], R [N, T, r] (then S [N, r] fp32 if want_s, the sweep counts [N] int32 if
+    want_info) of the truncated SVD of every block of image [E, T, Y, X] (dlcs_lr_decompose)."""
+    E, T, Y, X = image.shape
+    lr_check(E, T, b, r)
+    if r > T:
+        raise NotImplementedError(f"low-rank block SVD: rank {r} above the {T} columns of a block")
+    _lr_c64(win, win, image)
+    N = lr_num_blocks(Y, X, b)
+    L = empty((N, E * b * b, r), torch.complex64, image.device)
+    R = empty((N, T, r), torch.complex64, image.device)
+    sv = empty((N, r), torch.float32, image.device) if want_s else None
+    info = empty((N,), torch.int32, image.device) if want_info else None
+    call("dlcs_lr_decompose", p(image), p(win), p(L), p(R), p(sv), p(info), E, T, Y, X, b, r, S())
+    return (L, R) + ((sv,) if want_s else ()) + ((info,) if want_info else ())
+
+
 # ---------------------------------------------------------------------------- plane conv (conv2d.hip)
 # bf16 rows [N H W, ld], row = (n H + h) W + w; planes = (N, H, W, KH): KH 3 = N planes of H x W,
 # KH 1 = N H sequences of length W (dlcs.h "Plane conv").

@@ -3,15 +3,16 @@
 ArrayToBlocks cuts one dynamic image [1, E, T, Y, X] into N overlapping b x b blocks
 [N, E b^2, T] (stride b / 2, sqrt-Hann window, zero pad; lr:47-96, :149-161) and folds
 them back (lr:98-178).  Decompose factors every block into L [N, E b^2, r] and
-R [N, T, r] by a truncated SVD on the host (lr:213-238).
+R [N, T, r] by a truncated SVD: on the host (lr:213-238), or with svd='device' by
+dlcs_lr_decompose, one Jacobi SVD per block in LDS, straight from the GPU image.
 
-On GPU tensors the five dlcs_lr_* kernels do the work: extract, combine, and the fused
+On GPU tensors the dlcs_lr_* kernels do the work: extract, combine, and the fused
 compose (L, R -> image), project_l (image, R -> extract(image) R) and project_r
 (image, L -> extract(image)^H L), which never store the block tensor.  There is no
 fallback for GPU tensors outside the kernels' range (NotImplementedError).  CPU tensors
 go through plain torch ops: preprocessing runs in loader workers.  GPU tensors need an
 operator that was moved to the same GPU (`.to(device)`) and complex64 data; an operator left
-on the host (Decompose's always is: its SVD runs there) raises DlcsError, as mixed devices
+on the host (Decompose(svd='host')'s always is: its SVD runs there) raises DlcsError, as mixed devices
 do in SenseModel.
 
 The `divide` flag of the kernels: combine(divide=1) is the reference's combine (fold,
@@ -261,20 +262,48 @@ class ArrayToBlocks(nn.Module):
         return self.combine(input) if adjoint else self.extract(input)
 
 
+def decompose_blocks(image, op, rank, return_s=False, return_info=False):
+    """The raw dlcs_lr_decompose call: image [E, T, Y, X] (or [1, E, T, Y, X]) complex64 on the
+    GPU -> (L [N, E b^2, r], R [N, T, r][, S [N, r]][, sweeps [N]]) of the truncated SVD of
+    every block of op's geometry; op's win1d must be on the image's GPU."""
+    return _ops.lr_decompose(_img4(op, image), op.win1d, op.block_size, rank, want_s=return_s, want_info=return_info)
+
+
 class Decompose(nn.Module):
     """lr:190-262 -- blocks of [1, E, T, Y, X] factored into L [N, E b^2, r] and
-    R [N, T, r] (L = U sqrt(S), R = V sqrt(S) of the truncated SVD), and compose()."""
+    R [N, T, r] (L = U sqrt(S), R = V sqrt(S) of the truncated SVD), and compose().
+
+    svd='host' (the default) is the reference's path: blocks and torch.linalg.svd on the host,
+    the factors copied to the image's device.  svd='device' takes a GPU image and factors every
+    block in one dlcs_lr_decompose launch (one-sided Jacobi in LDS); the factors stay on the
+    GPU.  Its singular pairs carry the kernel's phase convention (the largest entry of R_k real
+    and positive), not LAPACK's: L R^H is the same, L and R differ by a unit phase per column."""
 
     def __init__(self, block_size: int, rank: int, image_shape: List[int], overlapping: Optional[bool] = False,
-                 device: str = 'cpu') -> None:
+                 device: str = 'cpu', svd: str = 'host') -> None:
         super().__init__()
         assert device == 'cpu'                                    # the SVD runs on the host (lr:206-207)
+        assert svd in ('host', 'device'), svd
         self.block_size = block_size
         self.rank = rank
+        self.svd = svd
         self.block_op = ArrayToBlocks(block_size, image_shape, overlapping).to(device)
+        self._gpu_ops = {}                                        # svd='device': the operator per GPU
+
+    def _op_on(self, device):
+        """The operator whose buffers live on `device` (built lazily, one per GPU)."""
+        if device.type != 'cuda':
+            return self.block_op
+        if device not in self._gpu_ops:
+            self._gpu_ops[device] = ArrayToBlocks(self.block_size, self.block_op.image_shape, True).to(device)
+        return self._gpu_ops[device]
 
     def decompose(self, images: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         rk = self.rank
+        if self.svd == 'device':
+            if not images.is_cuda:
+                raise _lib.DlcsError("Decompose(svd='device') takes an image on the GPU")
+            return decompose_blocks(images, self._op_on(images.device), rk)
         dev = images.device
         blocks = self.block_op(images.cpu() if images.is_cuda else images)
         U, S, Vh = torch.linalg.svd(blocks, full_matrices=False)
@@ -287,7 +316,7 @@ class Decompose(nn.Module):
         return _bt(matrix_batch)
 
     def compose(self, L: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
-        return compose(L, R, self.block_op)
+        return compose(L, R, self._op_on(L.device) if self.svd == 'device' else self.block_op)
 
     def forward(self, data, adjoint=False):
         if adjoint:

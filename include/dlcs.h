@@ -853,6 +853,28 @@ int dlcs_lr_project_l(const void* image, const void* R, const float* weights, co
 int dlcs_lr_project_r(const void* image, const void* L, const float* weights, const float* win, int divide, void* out,
                       int64_t E, int64_t T, int64_t Y, int64_t X, int64_t b, int64_t r, dlcs_stream_t stream);
 
+/* decompose (lowrank Decompose.decompose :213-238 without the host): the truncated SVD of
+ * every block of extract(image) (divide 0; the same geometry, block order and row order),
+ * one workgroup per block, the block matrix held in LDS and never stored.
+ *   B_n = U S V^H, singular values descending (ties: the lower column of the iteration first)
+ *   L [N, E b^2, r] = U[:, :r] sqrt(S_r),  R [N, T, r] = V[:, :r] sqrt(S_r)
+ *   S [N, r] fp32 = S_r,  info [N] int32 = the sweeps run;  both optional (NULL)
+ * Algorithm: Hestenes one-sided Jacobi in fp32 on the columns of B, V accumulated from the
+ * identity; pairs in round-robin tournament order (T - 1 steps of T / 2 disjoint pairs, a
+ * bye for odd T), a pair rotated when |a_p^H a_q| > 2^-23 ||a_p|| ||a_q||; sweeps until one
+ * rotates nothing, at most 30 (a block that gets there is written as it stands, info 30).
+ * A column whose squared norm is <= 2^-40 of the block's largest initial squared column norm
+ * is null: it is never rotated, and a component with a null sigma^2 is written as zeros in
+ * L and R (an all-zero block gives zeros, never NaN).
+ * Phase convention: each pair (L_k, R_k) is multiplied by the unit phase that makes the
+ * entry of R_k of largest magnitude real and positive (the lowest t on an exact tie), so
+ * the factors are a property of the data.  They are not LAPACK's phases.
+ * No float atomics: the same input gives the same bits.  Supported: the range above and
+ * r <= T; beyond, DLCS_ERR_UNSUPPORTED_SIZE and nothing is written.  No workspace; uses up
+ * to 136 KiB of LDS (T = 32, E b^2 = 512).                                              */
+int dlcs_lr_decompose(const void* image, const float* win, void* L, void* R, float* S, int32_t* info, int64_t E,
+                      int64_t T, int64_t Y, int64_t X, int64_t b, int64_t r, dlcs_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Plane conv (conv2d.hip): the bf16 k = 3 convolution of the DSLR family's 2-D and 1-D
  * ResNets (resnet2d.py, resnet1d.py) over independent planes, fp32 accumulation.

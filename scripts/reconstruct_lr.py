@@ -11,7 +11,8 @@ changes:
   * transform: the inference preprocessing of dl_cs.data.preprocess.DataTransform on the GPU
     (mask from the data, fftmod, 95th-percentile scale of the time-averaged adjoint,
     sliding-window initial image when SLWIN_INIT), then lowrank.Decompose of the initial image
-    into the block factors L_init, R_init (the truncated SVD runs on the host);
+    into the block factors L_init, R_init: the truncated SVD runs on the host, or with
+    --svd device on the GPU (dlcs_lr_decompose; use the setting the checkpoint was trained with);
   * forward: model(y, A=SenseModel(maps, weights=mask), BlockOp=ArrayToBlocks(block size,
     image shape), L0, R0) under no_grad, one ArrayToBlocks per image shape; the images are
     rescaled by the transform's scale.
@@ -29,19 +30,29 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from reconstruct import CflDataset, create_arg_parser, logger  # noqa: E402,F401
+import reconstruct  # noqa: E402
+from reconstruct import CflDataset, logger  # noqa: E402,F401
 import train_lr  # noqa: E402
 
 from dl_cs import checkpoint  # noqa: E402
 from dl_cs.config import load_cfg  # noqa: E402
 
 
+def create_arg_parser():
+    """reconstruct.py's command line plus --svd."""
+    parser = reconstruct.create_arg_parser()
+    parser.add_argument('--svd', choices=['host', 'device'], default='host',
+                        help='factor the initial image on the host (torch.linalg.svd) or on the GPU (block SVD kernel)')
+    return parser
+
+
 class LrTransform:
     """reconstruct_lr.py's DataTransform: (kspace, maps, mask, L_init, R_init, scale) of one
     example, kspace [C, T, Y, X] and maps [E, C, 1, Y, X] as CflDataset yields them."""
 
-    def __init__(self, config, device):
+    def __init__(self, config, device, svd='host'):
         from dl_cs.data.preprocess import DataTransform
+        self.svd = svd
         D = config.MODEL.PARAMETERS.DSLR
         self.block_size, self.num_basis, self.overlapping = D.BLOCK_SIZE, D.NUM_BASIS, D.OVERLAPPING
         self.base = DataTransform(config, device=device)
@@ -52,7 +63,7 @@ class LrTransform:
         from dl_cs.mri import lowrank
         if shape not in self._decompose:
             self._decompose[shape] = lowrank.Decompose(self.block_size, self.num_basis, list(shape),
-                                                       overlapping=self.overlapping)
+                                                       overlapping=self.overlapping, svd=self.svd)
         return self._decompose[shape]
 
     def __call__(self, kspace, maps):
@@ -104,7 +115,7 @@ def main(args):
     logger.info('Running inference...')
     start = time.time()
     D = config.MODEL.PARAMETERS.DSLR
-    images = run(model, LrTransform(config, device), data, D.BLOCK_SIZE, D.OVERLAPPING, device)
+    images = run(model, LrTransform(config, device, svd=getattr(args, 'svd', 'host')), data, D.BLOCK_SIZE, D.OVERLAPPING, device)
     logger.info(f'Elapsed time (reconstruction): {time.time() - start} s')
     logger.info('Writing images...')
     data.write(os.path.join(args.directory, args.out), images)

@@ -10,7 +10,8 @@ and checkpoint conventions) with the three things train_lr.py changes:
     so that checkpoints written under either name agree; AltMinCGv2 is reachable from
     Python only;
   * data: CinePreprocess(lr_decom=True), whose 8-tuple carries the initial block
-    factors L_init, R_init (train_lr.py:118, :186-200);
+    factors L_init, R_init (train_lr.py:118, :186-200); --svd device factors them on the
+    GPU (dlcs_lr_decompose) instead of the host, with the kernel's phase convention;
   * forward: model(y, A=SenseModel(maps, weights=mask), BlockOp=ArrayToBlocks(block
     size, target shape), L0, R0) (train_lr.py:120-125), batch size 1.
 """
@@ -47,7 +48,8 @@ class LrTrainer(TS.Trainer):
         super().__init__(config, args, rank, world, device)
 
     def preprocess(self, cls, use_seed):
-        return cls(self.cfg, lr_decom=True, use_seed=use_seed, device=self.device)
+        return cls(self.cfg, lr_decom=True, use_seed=use_seed, device=self.device,
+                   lr_svd=getattr(self.args, 'svd', 'host'))
 
     def block_op(self, shape):
         """ArrayToBlocks of an image shape, built once per shape (train_lr.py:121 builds one per step)."""
@@ -71,8 +73,17 @@ class LrTrainer(TS.Trainer):
         return pred, target
 
 
+def create_arg_parser():
+    p = TS.create_arg_parser()
+    p.add_argument('--svd', choices=['host', 'device'], default='host',
+                   help="where the initial image is factored into L, R: torch.linalg.svd on the host (the "
+                        "reference's) or the block SVD kernel on the GPU; its factors carry other phases, so "
+                        "reconstruct with the setting a checkpoint was trained with")
+    return p
+
+
 def main(argv=None):
-    args = TS.create_arg_parser().parse_args(argv)
+    args = create_arg_parser().parse_args(argv)
     args.builder = build_model
     args.trainer = 'lr'
     TS.main_args(args)

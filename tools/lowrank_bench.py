@@ -12,7 +12,12 @@ from them at the shipped configuration (configs/config_dslr.yaml): E, T, Y, X = 
   c. one forward + backward of the 2-D and of the 1-D CNN (2 resblocks, 128 features) in both
      compute dtypes -- fp32 on the generic conv3d_k3 kernels with the 3 x 3 / 3-tap weights
      embedded in 27 taps, bf16 on the plane conv (csrc/conv2d.hip) -- beside one 10-step CG
-     solve for L (11 normal applications).
+     solve for L (11 normal applications);
+  d. the initialiser: dlcs_lr_decompose (the block SVD kernel, HIP events) against
+     Decompose(svd='host') called with the same GPU image (copy to the host, extract and
+     torch.linalg.svd there, copy back; wall time around a synchronised call), on a rank-r
+     image with 1 % noise and on a Gaussian image, with the kernel's sweep counts
+     (--svd-only runs this part alone).
 
 One process; the variants alternate inside every round; each sample is HIP events around
 `reps` calls after a warm-up; median and minimum over the rounds.  --markdown FILE writes the
@@ -20,18 +25,62 @@ tables of DESIGN.md's section from the medians.
 """
 import argparse
 import os
+import statistics
 import sys
+import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from se_bench import DEV, HBM_PEAK, emit, interleaved  # noqa: E402  (also puts the package on sys.path)
+from se_bench import DEV, HBM_PEAK, emit, interleaved, sample  # noqa: E402  (also puts the package on sys.path)
 
 from dl_cs.models import _ops as K  # noqa: E402
 
 
 def crandn(*shape):
     return torch.randn(*shape, dtype=torch.complex64, device=DEV)
+
+
+def svd_part(args, lr, op, md):
+    """d. the initialiser on the device against the host path, in the same process."""
+    E, Tt, Y, X = args.shape
+    b, r = args.block, args.rank
+    host = lr.Decompose(b, r, [1, E, Tt, Y, X], True)
+    u, v = crandn(r, E, 1, Y, X), crandn(r, 1, Tt, 1, 1)
+    scale = (0.75 ** torch.arange(r, device=DEV, dtype=torch.float32)).reshape(r, 1, 1, 1, 1)
+    images = {"rank-r + 1 % noise": ((scale * u * v).sum(0) + 0.01 * crandn(E, Tt, Y, X)).contiguous(),
+              "Gaussian": crandn(E, Tt, Y, X)}
+    md += ["", "| initial factors of one image | median ms | min ms | sweeps (blocks) |", "|---|---|---|---|"]
+    for tag, img in images.items():
+        dev_fn = lambda: lr.decompose_blocks(img, op, r)
+
+        def host_fn():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            host(img[None])
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e6
+        for _ in range(3):
+            dev_fn()
+        host_fn()
+        td, th = [], []
+        for _ in range(args.rounds):                       # the two alternate inside every round
+            td.append(sample(dev_fn, args.reps))
+            th.append(host_fn())
+        info = lr.decompose_blocks(img, op, r, return_info=True)[2].cpu()
+        hist = {int(k): int((info == k).sum()) for k in info.unique()}
+        Ld, Rd = dev_fn()
+        Lh, Rh = host(img[None])
+        ref = torch.bmm(Lh, Rh.conj().transpose(1, 2))
+        diff = float((torch.bmm(Ld, Rd.conj().transpose(1, 2)) - ref).norm() / ref.norm())
+        for name, t in (("dlcs_lr_decompose", td), ("Decompose(svd='host'), GPU image", th)):
+            emit(dict(what="decompose", image=tag, variant=name, median_us=statistics.median(t), min_us=min(t),
+                      sweeps=hist, device_vs_host_nrmse=diff), args.out)
+        hs = ", ".join(f"{k}: {n}" for k, n in hist.items())
+        md += [f"| dlcs_lr_decompose, {tag} | {statistics.median(td) / 1e3:.3f} | {min(td) / 1e3:.3f} | {hs} |",
+               f"| Decompose(svd='host') on the same GPU image, copies included | {statistics.median(th) / 1e3:.1f} | "
+               f"{min(th) / 1e3:.1f} | |"]
+        md += [f"| L R^H of the two, NRMSE | {diff:.2e} | | |"]
 
 
 def main():
@@ -45,6 +94,7 @@ def main():
     ap.add_argument("--cg-steps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--svd-only", action="store_true", help="only part d, the initialiser")
     ap.add_argument("--out", default=None, help="append one JSON line per measurement")
     ap.add_argument("--markdown", default=None, help="write the result tables as markdown")
     args = ap.parse_args()
@@ -62,6 +112,10 @@ def main():
     c8 = lambda t: t.numel() * 8
     md = [f"Shapes: image {E} x {Tt} x {Y} x {X} ({c8(img) / 1e6:.1f} MB), {N} blocks of {b} x {b}, block tensor "
           f"{c8(blocks) / 1e6:.1f} MB, L {c8(L) / 1e6:.1f} MB, R {c8(R) / 1e6:.2f} MB; rank {r}, {C} coils.", ""]
+    if args.svd_only:
+        with torch.no_grad():
+            svd_part(args, lr, op, md)
+        return finish(md, args)
 
     # ---- a. the five kernels
     nbytes = {"extract": c8(img) + c8(blocks), "combine": c8(blocks) + c8(img), "compose": c8(L) + c8(R) + c8(img),
@@ -146,6 +200,12 @@ def main():
            f"{ms('cnn1d_fwd_bwd_bf16')} | {ratio('cnn1d_fwd_bwd')} |",
            f"| one {args.cg_steps}-step CG solve for L, forward ({args.cg_steps + 1} normal applications) | "
            f"{ms('cg_solve_L')} | | | |"]
+    with torch.no_grad():
+        svd_part(args, lr, op, md)
+    finish(md, args)
+
+
+def finish(md, args):
     text = "\n".join(md) + "\n"
     print(text)
     if args.markdown:
