@@ -3,6 +3,7 @@
 // the thin ends from fp32 rows (conv3d_thin_f16x3.inc) or planes (conv3d_thin_planes.inc).
 #include "conv3d_common.h"
 #include "f16x3_common.h"
+#include "wgrad_live.h"
 #include <type_traits>
 
 namespace {
@@ -245,6 +246,13 @@ size_t dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t 
 int dlcs_conv3d_k3_wgrad_f16x3(const void* xplanes, const void* gplanes, float* dw_packed, int64_t B, int64_t D,
                                int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
                                dlcs_stream_t stream) {
+    return dlcs_conv3d_k3_wgrad_f16x3_live(xplanes, gplanes, dw_packed, B, D, H, W, 0, D, workspace, workspace_bytes,
+                                           stream);
+}
+
+int dlcs_conv3d_k3_wgrad_f16x3_live(const void* xplanes, const void* gplanes, float* dw_packed, int64_t B, int64_t D,
+                                    int64_t H, int64_t W, int64_t t_lo, int64_t t_hi, void* workspace,
+                                    size_t workspace_bytes, dlcs_stream_t stream) {
     DLCS_CHECK_ARG(xplanes && gplanes && dw_packed && B > 0);
     const long rows = (long)B * D * H * W;
     if (D % 4 || H % 4 || W % 4 || !al16(xplanes) || !al16(gplanes) || rows * 320 >= (1L << 40))
@@ -256,7 +264,9 @@ int dlcs_conv3d_k3_wgrad_f16x3(const void* xplanes, const void* gplanes, float* 
     if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(B, D, H, W)))
         return DLCS_ERR_WORKSPACE;
     v.part = static_cast<float*>(workspace);
-    return wgrad_f16x3_launch(v, (hipStream_t)stream);
+    const int lo = (int)std::max<int64_t>(0, std::min<int64_t>(t_lo, D));
+    const int hi = (int)std::max<int64_t>(0, std::min<int64_t>(t_hi, D));
+    return wgrad_f16x3_launch(v, lo, hi, (hipStream_t)stream);
 }
 
 size_t dlcs_conv3d_thin_pack_f16x3_bytes(int kind) {
@@ -355,6 +365,14 @@ int dlcs_conv3d_thin_wgrad_f16x3(const float* in, int64_t cin, int64_t cin_ld, c
 int dlcs_conv3d_thin_out_planes_f16x3(const void* xplanes, const void* wthin, const float* bias, float* out,
                                       int64_t cout, int64_t cout_ld, int64_t B, int64_t D, int64_t H, int64_t W,
                                       int accumulate, int relu_out, dlcs_stream_t stream) {
+    return dlcs_conv3d_thin_out_planes_f16x3_slabs(xplanes, wthin, bias, out, cout, cout_ld, B, D, H, W, accumulate,
+                                                   relu_out, 0, D / 4, stream);
+}
+
+int dlcs_conv3d_thin_out_planes_f16x3_slabs(const void* xplanes, const void* wthin, const float* bias, float* out,
+                                            int64_t cout, int64_t cout_ld, int64_t B, int64_t D, int64_t H, int64_t W,
+                                            int accumulate, int relu_out, int64_t tb0, int64_t tb1,
+                                            dlcs_stream_t stream) {
     DLCS_CHECK_ARG(xplanes && wthin && out && B > 0 && cout >= 1 && cout <= 4 && cout_ld >= 4);
     if (D % 4 || H % 4 || W % 4 || cout_ld % 4 || !al16(xplanes) || !al16(wthin) || !al16(out))
         return DLCS_ERR_UNSUPPORTED_SIZE;
@@ -363,7 +381,9 @@ int dlcs_conv3d_thin_out_planes_f16x3(const void* xplanes, const void* wthin, co
     v.B = (int)B; v.D = (int)D; v.H = (int)H; v.W = (int)W;
     v.cout_ld = (int)cout_ld; v.accumulate = accumulate; v.relu_out = relu_out; v.cout = (int)cout;
     v.cout_pad = (int)cout;
-    return conv_thin_out_p_launch(v, (const f16*)xplanes, (const f16*)wthin, (hipStream_t)stream);
+    const int64_t nT = D / 4;
+    const int s0 = (int)std::max<int64_t>(0, std::min(tb0, nT)), s1 = (int)std::max<int64_t>(0, std::min(tb1, nT));
+    return conv_thin_out_p_launch(v, (const f16*)xplanes, (const f16*)wthin, s0, s1, (hipStream_t)stream);
 }
 
 size_t dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes(void) { return (size_t)kTwpWG * 160 * 128 * sizeof(float); }
@@ -372,6 +392,18 @@ int dlcs_conv3d_thin_wgrad_planes_f16x3(const void* bigplanes, const float* thin
                                         const unsigned* thin_max, int big_is_co, float* dw_packed, int64_t cout_pad,
                                         int64_t cin_pad, int64_t B, int64_t D, int64_t H, int64_t W, void* workspace,
                                         size_t workspace_bytes, dlcs_stream_t stream) {
+    return dlcs_conv3d_thin_wgrad_planes_f16x3_live(bigplanes, thin, thin_ch, thin_ld, thin_max, big_is_co, dw_packed,
+                                                    cout_pad, cin_pad, B, D, H, W, 0, D, workspace, workspace_bytes,
+                                                    stream);
+}
+
+int dlcs_conv3d_thin_wgrad_planes_f16x3_live(const void* bigplanes, const float* thin, int64_t thin_ch,
+                                             int64_t thin_ld, const unsigned* thin_max, int big_is_co,
+                                             float* dw_packed, int64_t cout_pad, int64_t cin_pad, int64_t B, int64_t D,
+                                             int64_t H, int64_t W, int64_t t_lo, int64_t t_hi, void* workspace,
+                                             size_t workspace_bytes, dlcs_stream_t stream) {
+    // the window is on the thin operand as g (the final conv's shape)
+    DLCS_CHECK_ARG(!big_is_co || (t_lo <= 0 && t_hi >= D));
     DLCS_CHECK_ARG(bigplanes && thin && thin_max && dw_packed && B > 0 && thin_ch >= 1 && thin_ch <= 4 &&
                    thin_ld >= 4);
     if (D % 4 || H % 4 || W % 4 || thin_ld % 4 || !al16(bigplanes) || !al16(thin) ||
@@ -386,7 +418,8 @@ int dlcs_conv3d_thin_wgrad_planes_f16x3(const void* bigplanes, const float* thin
     if (!ws_ok(workspace, workspace_bytes, dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes()))
         return DLCS_ERR_WORKSPACE;
     t.part = static_cast<float*>(workspace);                 // one [160][128] slab per workgroup
-    return wgrad_thin_p_launch(t, (hipStream_t)stream);
+    const int lo = (int)std::max<int64_t>(0, std::min(t_lo, D)), hi = (int)std::max<int64_t>(0, std::min(t_hi, D));
+    return wgrad_thin_p_launch(t, lo, hi, (hipStream_t)stream);
 }
 
 }  // extern "C"

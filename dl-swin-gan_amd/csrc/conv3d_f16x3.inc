@@ -599,7 +599,23 @@ struct WgradH3Args {
     int B, D, H, W;
 };
 
-__global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, int nrange, int ppr) {
+// Live-frame window (WIN).  The caller promises that g is exactly zero outside
+// frames [t_lo, t_hi) of every batch item (the crop of the network's circular time
+// pad: its backward writes zero frames, and each k3 input gradient widens the band
+// by one frame per side).  A half patch covers two frames, so the live units are
+// the half-slabs hs = 2 t_blk + th in [hs_lo, hs_hi) = [t_lo / 2, ceil(t_hi / 2)) of
+// each batch item, walked in the same patch-major order: the first live slab may
+// have its second half alone, the last its first half alone, every slab between
+// both.  The ranges are cut in live-unit space (sizes differ by at most one unit),
+// dead units are neither DMA'd nor multiplied, and the DMA stream follows the live
+// sequence one unit at a time (wgl_advance, wgrad_live.h) instead of "unit u + 2 =
+// the same half of the next patch"; the half is then a wave-uniform scalar.  The
+// prologue stays straight-line code: as a loop it cost five reloads of spilled LDS
+// offsets per unit.  WIN = false is the kernel without a window.
+struct WgradH3Live { int hs_lo, hs_hi, upr, urem; };   // ranges: upr units each, the first urem one more
+
+template <bool WIN>
+__global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, int nrange, int ppr, WgradH3Live lv) {
     __shared__ __attribute__((aligned(16))) f16 smem_wh[3 * kWhBuf];     // 153.6 KB: a 3-unit ring
     const int b = blockIdx.x;
     int range, grp;
@@ -618,7 +634,11 @@ __global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, 
     const int nYX = nY * nX;
     const int npatch = a.B * nT * nYX;
     const int p0 = range * ppr, p1 = min(npatch, p0 + ppr);
-    if (p0 >= p1) return;
+    if (!WIN && p0 >= p1) return;
+    // WIN: this range's live units [lu0, lu1), never empty (the launch has nrange <= live units)
+    const WgLiveGeom lg{nT, nY, nX, lv.hs_lo, lv.hs_hi};
+    int lu0, lu1;
+    wgl_range(lv.upr, lv.urem, range, &lu0, &lu1);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int kwi = wave >> 2, coh = (wave >> 1) & 1, cih = wave & 1;
     // rows below the current patch a halo row may reach (t, y, x neighbours): the
@@ -661,8 +681,12 @@ __global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, 
     }
     const unsigned dst0 = __builtin_amdgcn_readfirstlane(lds_offset(smem_wh));
     // the unit's patch: flat index ip and (t, y, x) coordinates, advanced with carries
-    int ip = p0, ipt, ipy, ipx;
-    {
+    // (WIN: of the unit the DMA stream stands at, with its half in it.th)
+    WgLiveIter it{};
+    int &ip = it.ip, &ipt = it.ipt, &ipy = it.ipy, &ipx = it.ipx;
+    if (WIN) it = wgl_seek(lg, lu0);
+    else {
+        ip = p0;
         const int r = ip % (nT * nYX);
         ipt = r / nYX;
         ipy = (r / nX) % nY;
@@ -726,7 +750,21 @@ __global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, 
     const int xrow = (32 + ((gq >> 1) * 4 + 2 * swb) * 6 + q + kwi) * 160;
 
     // prologue: both halves of the first patch (units u0, u0 + 1) into buffers 0, 1
-    {
+    // (WIN: the first two live units, each with its own patch and half)
+    if (WIN) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (lu0 + s < lu1) {
+                const char *gb, *xb;
+                unsigned xz;
+                bases(gb, xb, xz);
+                const unsigned miss = missing();
+#pragma unroll
+                for (int k = 0; k < 5; ++k) issue_piece(k, it.th, s, miss, gb, xb, xz);
+                wgl_advance(lg, it);
+            }
+        }
+    } else {
         const char *gb, *xb;
         unsigned xz;
         bases(gb, xb, xz);
@@ -736,7 +774,7 @@ __global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, 
 #pragma unroll
         for (int k = 0; k < 5; ++k) issue_piece(k, 1, 1, miss, gb, xb, xz);
     }
-    next_patch();                                    // ip = the patch of units u0 + 2, u0 + 3
+    if (!WIN) next_patch();                          // ip = the patch of units u0 + 2, u0 + 3
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int cur = 0;
@@ -786,10 +824,18 @@ __global__ void __launch_bounds__(768) conv3d_wgrad_f16x3_kernel(WgradH3Args a, 
         __syncthreads();
         cur = cur == 2 ? 0 : cur + 1;
     };
-    for (int u = 2 * p0; u < 2 * p1; ++u) {
-        const int th = u & 1;
-        unit(th, (u >> 1) + 1 < p1);
-        if (th) next_patch();
+    if (WIN) {
+        // the stream stands at live unit u + 2, whose half is the scalar it.th
+        for (int u = lu0; u < lu1; ++u) {
+            unit(it.th, u + 2 < lu1);
+            wgl_advance(lg, it);
+        }
+    } else {
+        for (int u = 2 * p0; u < 2 * p1; ++u) {
+            const int th = u & 1;
+            unit(th, (u >> 1) + 1 < p1);
+            if (th) next_patch();
+        }
     }
     // raw partial of this (range, tap row): part[range][tap][co][ci], 16-B row stores
     // after a transpose through LDS (each wave's 80 x 80 block; the ring is free now)
@@ -834,9 +880,13 @@ static PatchRanges wgh3_ranges(long npatch, bool bound) {
     return patch_ranges(npatch, bound ? kWgH3MaxRanges : env_nr > 0 ? std::min(env_nr, kWgH3MaxRanges) : 28);
 }
 
-// a.part: wgh3_ranges(npatch, true).nr slabs
-static int wgrad_f16x3_launch(const WgradH3Args& a, hipStream_t st) {
+// a.part: wgh3_ranges(npatch, true).nr slabs.  [t_lo, t_hi): the frames of every batch item
+// outside which g is exactly zero (the caller's promise); [0, D) or wider = no window.
+static int wgrad_f16x3_launch(const WgradH3Args& a, int t_lo, int t_hi, hipStream_t st) {
     const long npatch = (long)a.B * (a.D / 4) * (a.H / 4) * (a.W / 4);
+    int hs_lo, hs_hi;
+    wgl_halfslabs(a.D, t_lo, t_hi, &hs_lo, &hs_hi);
+    if (hs_lo >= hs_hi) return DLCS_OK;              // g = 0 everywhere: dW += 0
     // 32-bit lane offsets (16-B units << 7 in the kernel, relative to a base bias_rows below
     // the patch): 2 bias_rows + 2 patches within 2^25 x 16 B; the zero row's byte offset
     // from a unit base within 2^32
@@ -844,9 +894,18 @@ static int wgrad_f16x3_launch(const WgradH3Args& a, hipStream_t st) {
     if ((2 * bias_rows + 128) * 40 >= (1L << 25) || (npatch * 64 + bias_rows) * 640 + 1024 >= (1L << 32))
         return DLCS_ERR_UNSUPPORTED_SIZE;
     const PatchRanges r = wgh3_ranges(npatch, false);
-    const int nr = r.nr;
+    int nr = r.nr;
     const long pp = r.pp;
-    hipLaunchKernelGGL(conv3d_wgrad_f16x3_kernel, dim3((unsigned)(9 * nr)), dim3(768), 0, st, a, nr, (int)pp);
+    if (hs_lo == 0 && hs_hi == a.D / 2)
+        hipLaunchKernelGGL(conv3d_wgrad_f16x3_kernel<false>, dim3((unsigned)(9 * nr)), dim3(768), 0, st, a, nr, (int)pp,
+                           WgradH3Live{});
+    else {
+        // as many ranges as without a window (never more than live units), cut over the live units
+        const long nlive = (long)a.B * (hs_hi - hs_lo) * (a.H / 4) * (a.W / 4);
+        nr = (int)std::min<long>(nr, nlive);
+        hipLaunchKernelGGL(conv3d_wgrad_f16x3_kernel<true>, dim3((unsigned)(9 * nr)), dim3(768), 0, st, a, nr, (int)pp,
+                           WgradH3Live{hs_lo, hs_hi, (int)(nlive / nr), (int)(nlive % nr)});
+    }
     hipLaunchKernelGGL(wgrad_f16x3_reduce_kernel, dim3((unsigned)cdiv(27L * 160 * 40, 256)), dim3(256), 0, st, a, nr);
     return dlcs_launch_status();
 }

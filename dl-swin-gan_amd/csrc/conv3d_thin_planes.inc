@@ -206,8 +206,11 @@ DLCS_DEV void thin_out_p3_b(const f16* wimg, int cc, int kk0, int kg, int m, f16
     }
 }
 
+// Slab window [tb0, tb1) of the tile walk: only the tiles of those 4-frame slabs are
+// computed (their halos still reach into the slabs beside them), the output rows of the
+// other slabs are left untouched -- for a caller that never reads them.  [0, nT) = all.
 __global__ void __launch_bounds__(512, 1) conv3d_thin_out_p3_kernel(ConvF32Args a, const f16* xp, const f16* wimg,
-                                                                    long rows) {
+                                                                    long rows, int tb0, int tb1) {
     __shared__ __attribute__((aligned(16))) f16 smem_tp3[3 * kTpBuf];           // 135 KB
     const float sx = f16x3_scale(*reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(xp) + rows * 640));
     const float inv = 1.0f / (sx * *reinterpret_cast<const float*>(wimg + kThinOutHalfs));
@@ -234,15 +237,16 @@ __global__ void __launch_bounds__(512, 1) conv3d_thin_out_p3_kernel(ConvF32Args 
     const int npc = wave < kTpPieces - 40 ? 6 : 5;               // this wave's DMA instructions per item
     const unsigned dst0 = __builtin_amdgcn_readfirstlane(lds_offset(smem_tp3));
     const int nBY = (nYt + 3) >> 2, nBX = (nX + 7) >> 3;
-    const int nblocks = a.B * nT * nBY * nBX, xcd = blockIdx.x & 7, kw = blockIdx.x >> 3;
+    const int nTw = tb1 - tb0;
+    const int nblocks = a.B * nTw * nBY * nBX, xcd = blockIdx.x & 7, kw = blockIdx.x >> 3;
     const int nrounds = xcd < nblocks ? (nblocks - xcd + 7) >> 3 : 0;
     const int nitems = nrounds * 5;
     auto decode = [&](int r, int& b, int& pt, int& py2, int& px) {
         int bid = r * 8 + xcd;
         const int bx = bid % nBX; bid /= nBX;
         const int by = bid % nBY; bid /= nBY;
-        pt = bid % nT;
-        b = bid / nT;
+        pt = tb0 + bid % nTw;
+        b = bid / nTw;
         py2 = by * 4 + (kw >> 3);
         px = bx * 8 + (kw & 7);
         return py2 < nYt && px < nX;
@@ -365,8 +369,12 @@ __global__ void __launch_bounds__(512, 1) conv3d_thin_out_p3_kernel(ConvF32Args 
     }
 }
 
-static int conv_thin_out_p_launch(const ConvF32Args& v, const f16* xp, const f16* wimg, hipStream_t st) {
+static int conv_thin_out_p_launch(const ConvF32Args& v, const f16* xp, const f16* wimg, int tb0, int tb1,
+                                  hipStream_t st) {
     const int nT = v.D / 4, nY = v.H / 4, nX = v.W / 4;
+    tb0 = std::max(tb0, 0);
+    tb1 = std::min(tb1, nT);
+    if (tb0 >= tb1) return DLCS_OK;                  // no slab to compute
     const long rows = (long)v.B * v.D * v.H * v.W;
     const long bias_rows = ((long)nY * nX + nX + 1) * 64;
     // 16-B offsets relative to a base bias_rows below the tile (24 bits in the kernel);
@@ -377,10 +385,11 @@ static int conv_thin_out_p_launch(const ConvF32Args& v, const f16* xp, const f16
     // DLCS_THIN_OUT_P2=1 (DIAG build): the two-buffer kernel with LDS weights, for A/B timing
 #ifdef DLCS_DIAG_BUILD
     static const bool p2 = [] { const char* e = dlcs_knob("DLCS_THIN_OUT_P2"); return e && e[0] == '1'; }();
-    if (p2) hipLaunchKernelGGL(conv3d_thin_out_p_kernel, dim3(256), dim3(512), 0, st, v, xp, wimg, rows);
+    if (p2 && tb0 == 0 && tb1 == nT)
+        hipLaunchKernelGGL(conv3d_thin_out_p_kernel, dim3(256), dim3(512), 0, st, v, xp, wimg, rows);
     else
 #endif
-    hipLaunchKernelGGL(conv3d_thin_out_p3_kernel, dim3(256), dim3(512), 0, st, v, xp, wimg, rows);
+    hipLaunchKernelGGL(conv3d_thin_out_p3_kernel, dim3(256), dim3(512), 0, st, v, xp, wimg, rows, tb0, tb1);
     return dlcs_launch_status();
 }
 
@@ -398,6 +407,14 @@ static int conv_thin_out_p_launch(const ConvF32Args& v, const f16* xp, const f16
 // (16-column tiles swizzled as the Big image).  Patch p + 1's DMA runs during patch
 // p's products; 8 waves = 2 M halves x 4 N pairs.  Each workgroup stores its raw
 // [160][128] partial; wgrad_thin_p_reduce_kernel sums them in a fixed order.
+//
+// Live-frame window on the thin operand (final conv shape, lv.per > 0): the caller promises
+// that the thin tensor is exactly zero outside frames [t_lo, t_hi) of every batch item.  A
+// patch gathers it through a one-frame tap halo, so the patches of a 4-frame slab are dead iff
+// the slab's frames widened by one per side miss the window (wgl_slabs); the workgroups cut
+// their ranges over the live patches (sizes differ by at most one, empty ranges store zeros)
+// and dead patches are neither DMA'd nor multiplied.
+struct ThinWgPLive { int per, item, first, base, rem; };   // wgl_live_patch / wgl_range; per = 0: no window
 struct ThinWgPArgs {
     const f16* bp; const float* thin; float* dw; float* part;
     const unsigned* thin_max;
@@ -411,12 +428,15 @@ constexpr int kTwTR = 256 * 8;                           // f16 of raw thin rows
 constexpr int kTwBuf = kTwBigB + kTwTR;
 constexpr int kTwIm = 32 * 128;                          // f16 per im2col plane image (one unit)
 
-__global__ void __launch_bounds__(512, 1) conv3d_wgrad_thin_p_kernel(ThinWgPArgs a, int ppr) {
+__global__ void __launch_bounds__(512, 1) conv3d_wgrad_thin_p_kernel(ThinWgPArgs a, int ppr, ThinWgPLive lv) {
     __shared__ __attribute__((aligned(16))) f16 smem_twp[2 * kTwBuf + 4 * kTwIm];      // 121.6 KB
     f16* IM = smem_twp + 2 * kTwBuf;
     const int nT = a.D >> 2, nY = a.H >> 2, nX = a.W >> 2;
     const int npatch = a.B * nT * nY * nX;
-    const int p0 = (int)blockIdx.x * ppr, p1 = min(npatch, p0 + ppr);
+    // this workgroup's patches: numbers [p0, p1) of the live patches (no window: of all patches)
+    int p0 = (int)blockIdx.x * ppr, p1 = min(npatch, p0 + ppr);
+    if (lv.per) wgl_range(lv.base, lv.rem, (int)blockIdx.x, &p0, &p1);
+    auto patch_of = [&](int u) { return lv.per ? wgl_live_patch(u, lv.per, lv.item, lv.first) : u; };
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float st = f16x3_scale(*a.thin_max);
     // im2col padding columns 108..127 (tile 7 minus 4 columns) stay zero: rows x 20 columns
@@ -443,8 +463,9 @@ __global__ void __launch_bounds__(512, 1) conv3d_wgrad_thin_p_kernel(ThinWgPArgs
         pt = r % nT;
         bb = r / nT;
     };
-    auto issue = [&](int patch, int buf) {
-        if (patch >= p1) return;
+    auto issue = [&](int u, int buf) {
+        if (u >= p1) return;
+        const int patch = patch_of(u);
         const char* sb = reinterpret_cast<const char*>(a.bp) + (long)patch * 64 * 640;
         const unsigned dst = lds0 + (unsigned)(buf * kTwBuf * 2);
 #pragma unroll
@@ -466,8 +487,9 @@ __global__ void __launch_bounds__(512, 1) conv3d_wgrad_thin_p_kernel(ThinWgPArgs
     // im2col job of this thread (tid < 216): tap, 8-voxel chunk tc (t = tc >> 1, y pair tc & 1)
     const int jtap = tid >> 3, tc = tid & 7;
     const int skd = a.sgn * (jtap / 9 - 1), skh = a.sgn * ((jtap / 3) % 3 - 1), skw = a.sgn * (jtap % 3 - 1);
-    auto build = [&](int patch, int buf) {
+    auto build = [&](int u, int buf) {
         if (tid >= 216) return;
+        const int patch = patch_of(u);
         int bb, pt, py, px;
         coords(patch, bb, pt, py, px);
         const float* TR = reinterpret_cast<const float*>(smem_twp + buf * kTwBuf + kTwBigB);
@@ -586,11 +608,22 @@ __global__ void __launch_bounds__(256) wgrad_thin_p_reduce_kernel(ThinWgPArgs a,
 // a.part: partial slabs (256 workgroups x [160][128])
 constexpr int kTwpWG = 256;
 
-static int wgrad_thin_p_launch(const ThinWgPArgs& a, hipStream_t st) {
-    const long npatch = (long)a.B * (a.D / 4) * (a.H / 4) * (a.W / 4);
+// [t_lo, t_hi): the frames of every batch item outside which the thin tensor is exactly zero
+// (the caller's promise); [0, D) or wider = no window
+static int wgrad_thin_p_launch(const ThinWgPArgs& a, int t_lo, int t_hi, hipStream_t st) {
+    const int nT = a.D / 4, nYX = (a.H / 4) * (a.W / 4);
+    const long npatch = (long)a.B * nT * nYX;
     if (npatch * 64 * 640 >= (1L << 32)) return DLCS_ERR_UNSUPPORTED_SIZE;       // 32-bit DMA offsets
+    int s0, s1;
+    wgl_slabs(a.D, t_lo, t_hi, 1, &s0, &s1);
+    if (s0 >= s1) return DLCS_OK;                    // thin = 0 everywhere: dW += 0
     const int ppr = (int)((npatch + kTwpWG - 1) / kTwpWG);
-    hipLaunchKernelGGL(conv3d_wgrad_thin_p_kernel, dim3(kTwpWG), dim3(512), 0, st, a, ppr);
+    ThinWgPLive lv{};
+    if (s0 > 0 || s1 < nT) {
+        const int per = (s1 - s0) * nYX, n = a.B * per;
+        lv = ThinWgPLive{per, nT * nYX, s0 * nYX, n / kTwpWG, n % kTwpWG};
+    }
+    hipLaunchKernelGGL(conv3d_wgrad_thin_p_kernel, dim3(kTwpWG), dim3(512), 0, st, a, ppr, lv);
     hipLaunchKernelGGL(wgrad_thin_p_reduce_kernel, dim3(160 * 128 / 64), dim3(256), 0, st, a, kTwpWG);
     return dlcs_launch_status();
 }

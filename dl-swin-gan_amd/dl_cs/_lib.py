@@ -86,6 +86,7 @@ SIGNATURES = {
     "dlcs_gemm_f32_splitk_det_workspace_bytes": [_I64, _I64],
     "dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes": [_I64] * 4,
     "dlcs_conv3d_k3_wgrad_f16x3": [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _SZ, _P],
+    "dlcs_conv3d_k3_wgrad_f16x3_live": [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P],
     "dlcs_conv3d_k3_f16x3_workspace_bytes": [_I64, _I64, _I64, _I64, _INT],
     "dlcs_conv3d_k3_f16x3": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _F, _INT, _INT, _P, _P, _P,
                              _P, _P, _SZ, _P],
@@ -96,9 +97,13 @@ SIGNATURES = {
     "dlcs_conv3d_thin_f16x3": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P,
                                _I64, _F, _INT, _INT, _P, _P, _P, _P, _P, _SZ, _P],
     "dlcs_conv3d_thin_out_planes_f16x3": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _INT, _P],
+    "dlcs_conv3d_thin_out_planes_f16x3_slabs": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _INT, _I64,
+                                                _I64, _P],
     "dlcs_conv3d_thin_wgrad_planes_f16x3_workspace_bytes": [],
     "dlcs_conv3d_thin_wgrad_planes_f16x3": [_P, _P, _I64, _I64, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64,
                                             _P, _SZ, _P],
+    "dlcs_conv3d_thin_wgrad_planes_f16x3_live": [_P, _P, _I64, _I64, _P, _INT, _P, _I64, _I64, _I64, _I64, _I64, _I64,
+                                                 _I64, _I64, _P, _SZ, _P],
     "dlcs_conv3d_thin_wgrad_f16x3": [_P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _I64, _I64,
                                      _I64, _P],
     "dlcs_swin_pre": [_INT, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P],

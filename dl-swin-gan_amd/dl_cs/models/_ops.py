@@ -508,11 +508,17 @@ def linear_k160_f16x3(x_planes, M, w_planes, N, out, bias=None, act=0, aux=None,
     return out
 
 
-def conv3d_wgrad_f16x3(x_planes, g_planes, grid, dw_packed):
-    """dw_packed [27, 160, 160] += fp32 conv weight gradient from f16 plane pairs (dlcs_conv3d_k3_wgrad_f16x3)."""
+def conv3d_wgrad_f16x3(x_planes, g_planes, grid, dw_packed, live=None):
+    """dw_packed [27, 160, 160] += fp32 conv weight gradient from f16 plane pairs (dlcs_conv3d_k3_wgrad_f16x3).
+    live = (t_lo, t_hi): the caller's promise that g is exactly zero outside those frames of every
+    batch item; the kernel skips the work there (dlcs_conv3d_k3_wgrad_f16x3_live).  None: no window."""
     B, D, H, W = grid
     ws, nb = _ws("dlcs_conv3d_k3_wgrad_f16x3", dw_packed.device, B, D, H, W)
-    call("dlcs_conv3d_k3_wgrad_f16x3", p(x_planes), p(g_planes), p(dw_packed), B, D, H, W, p(ws), nb, S())
+    if live is None:
+        call("dlcs_conv3d_k3_wgrad_f16x3", p(x_planes), p(g_planes), p(dw_packed), B, D, H, W, p(ws), nb, S())
+    else:
+        call("dlcs_conv3d_k3_wgrad_f16x3_live", p(x_planes), p(g_planes), p(dw_packed), B, D, H, W, int(live[0]),
+             int(live[1]), p(ws), nb, S())
     return dw_packed
 
 
@@ -565,26 +571,40 @@ def conv3d_thin_wgrad_f16x3(x, cin, x_max, g, cout, g_max, grid, dw_packed, cols
     return dw_packed
 
 
-def conv3d_thin_out_planes(planes, wthin, cout, out_ld, grid, bias=None, out=None, accumulate=0, relu_out=0):
+def conv3d_thin_out_planes(planes, wthin, cout, out_ld, grid, bias=None, out=None, accumulate=0, relu_out=0,
+                           slabs=None):
     """fp32 thin-output conv3d_k3 (160 -> cout <= 4) from the split2 planes of its input
-    (dlcs_conv3d_thin_out_planes_f16x3); out fp32 [rows, out_ld]."""
+    (dlcs_conv3d_thin_out_planes_f16x3); out fp32 [rows, out_ld].  slabs = (tb0, tb1): only those
+    4-frame slabs of every batch item are computed, the rows of the others are left as they are
+    (uninitialised in a fresh `out`) and must not be read.  None: all."""
     B, D, H, W = grid
     rows = B * D * H * W
     if out is None:
         out = empty((rows, out_ld), torch.float32, planes.device)
-    call("dlcs_conv3d_thin_out_planes_f16x3", p(planes), p(wthin), p(bias), p(out), cout, out.shape[-1], B, D, H, W,
-         int(accumulate), int(relu_out), S())
+    if slabs is None:
+        call("dlcs_conv3d_thin_out_planes_f16x3", p(planes), p(wthin), p(bias), p(out), cout, out.shape[-1], B, D, H,
+             W, int(accumulate), int(relu_out), S())
+    else:
+        call("dlcs_conv3d_thin_out_planes_f16x3_slabs", p(planes), p(wthin), p(bias), p(out), cout, out.shape[-1], B,
+             D, H, W, int(accumulate), int(relu_out), int(slabs[0]), int(slabs[1]), S())
     return out
 
 
-def conv3d_thin_wgrad_planes(big_planes, thin, thin_ch, thin_max, big_is_co, grid, dw_packed):
+def conv3d_thin_wgrad_planes(big_planes, thin, thin_ch, thin_max, big_is_co, grid, dw_packed, live=None):
     """dw_packed [27, cout_pad, cin_pad] += fp32 weight gradient between the split2 planes of the
     160-channel operand and the fp32 thin tensor (dlcs_conv3d_thin_wgrad_planes_f16x3); big_is_co:
-    1 = SFE (planes = g), 0 = final conv (planes = its input)."""
+    1 = SFE (planes = g), 0 = final conv (planes = its input).  live = (t_lo, t_hi), big_is_co = 0
+    only: the caller's promise that thin (= g) is exactly zero outside those frames of every batch
+    item; patches whose one-frame halo misses them are skipped.  None: no window."""
     B, D, H, W = grid
     ws, nb = _ws("dlcs_conv3d_thin_wgrad_planes_f16x3", dw_packed.device)
-    call("dlcs_conv3d_thin_wgrad_planes_f16x3", p(big_planes), p(thin), thin_ch, thin.shape[-1], _word(thin_max),
-         int(big_is_co), p(dw_packed), dw_packed.shape[1], dw_packed.shape[2], B, D, H, W, p(ws), nb, S())
+    if live is None:
+        call("dlcs_conv3d_thin_wgrad_planes_f16x3", p(big_planes), p(thin), thin_ch, thin.shape[-1], _word(thin_max),
+             int(big_is_co), p(dw_packed), dw_packed.shape[1], dw_packed.shape[2], B, D, H, W, p(ws), nb, S())
+    else:
+        call("dlcs_conv3d_thin_wgrad_planes_f16x3_live", p(big_planes), p(thin), thin_ch, thin.shape[-1],
+             _word(thin_max), int(big_is_co), p(dw_packed), dw_packed.shape[1], dw_packed.shape[2], B, D, H, W,
+             int(live[0]), int(live[1]), p(ws), nb, S())
     return dw_packed
 
 

@@ -231,6 +231,32 @@ def _conv_flops(grid, cin, cout):
     return 2.0 * grid[0] * grid[1] * grid[2] * grid[3] * cout * cin * 27
 
 
+# Work not done on cropped frames.  The network pads the time axis circularly by `pad` frames
+# per side (swin_pre) and crops them after the final conv (swin_post), so on the padded axis of
+# D = T + 2 pad frames:
+#   forward:  swin_post reads the final conv's output on frames [pad, D - pad) only;
+#   backward: the crop's gradient `go` is exactly zero outside [pad, D - pad), and every k3
+#             conv input gradient on the way down (whatever mask or sign it applies: 0 stays 0,
+#             and the planes of 0 are 0) widens the non-zero band by one frame per side.
+# _live_frames(grid, pad, n) is the band after n such input gradients: n = 0 for go, 1 for g_h
+# (through the final conv), 2 for the last stage's g_out (through the DFE conv).  The embed
+# gradient below that is dense (4-frame patches, shifted windows): no window from there on.
+def _live_frames(grid, pad, nconv):
+    D = grid[1]
+    return max(pad - nconv, 0), min(D - pad + nconv, D)
+
+
+def _live_slabs(grid, pad):
+    """The 4-frame slabs that cover the frames swin_post reads."""
+    return pad // 4, (grid[1] - pad + 3) // 4
+
+
+def _wgrad_live_flops(grid, cin, cout, live):
+    """Flops of the f16x3 weight gradient's live units (two frames each) under the window `live`."""
+    frames = 2 * ((live[1] + 1) // 2 - live[0] // 2)
+    return _conv_flops((grid[0], frames, grid[2], grid[3]), cin, cout)
+
+
 def _timed_conv(*args, **kw):
     return _timed("conv_fwd", _conv_flops(args[5], args[1], args[3]), K.conv3d, *args, **kw)
 
@@ -516,7 +542,9 @@ def _split_forward(W, x, heads, window, pad, drop_scales):
     K.planes_bound(ph, rows, m0=inp_max, n0=W.dfe_norm, m1=word(0), c1=2.0, vec=P["dfe_tail.bias"])
     h = _timed("conv_fwd", flops, K.conv3d_f16x3, pout, W.dfe, grid, bias=P["dfe_tail.bias"], res=s,
                res_scale=2.0, relu_out=1, out_max=K.p(hmax), out_planes=ph, planes_only=not keep_fp32)
-    o = K.conv3d_thin_out_planes(ph, W.fin_h3, cin, PAD_CIN, grid, bias=P["final_layer.layers.2.conv.bias"])
+    # only the slabs swin_post reads are computed; the other rows of o stay uninitialised
+    o = K.conv3d_thin_out_planes(ph, W.fin_h3, cin, PAD_CIN, grid, bias=P["final_layer.layers.2.conv.bias"],
+                                 slabs=_live_slabs(grid, pad))
     out = K.swin_post(o, (B, E, T, Y, X), pad)                                       # s3d:408-418
     saved = dict(u=u, s=s, b=b, pout=pout, h=h, ph=ph, stages=stages, geos=geos, shape=(B, E, T, Y, X), grid=grid,
                  pad=pad, heads=heads, cin=cin, C=C, ntok=ntok, umax=umax, hmax=hmax)
@@ -646,10 +674,11 @@ def _split_backward(W, sv, gout, grads):
     flops = _conv_flops(grid, C, C)
     go = K.swin_post_bwd(gout.contiguous(), dtype, pad, PAD_CIN)
 
-    def split_wgrad(x_planes, g_planes, wname):
-        # the bias gradient came with the planes of g (colsum)
+    def split_wgrad(x_planes, g_planes, wname, live=None):
+        # the bias gradient came with the planes of g (colsum); live: g's non-zero frames
         dwp = torch.zeros((27, C, C), dtype=torch.float32, device=dev)
-        _timed("conv_wgrad", flops, K.conv3d_wgrad_f16x3, x_planes, g_planes, grid, dwp)
+        _timed("conv_wgrad", flops if live is None else _wgrad_live_flops(grid, C, C, live), K.conv3d_wgrad_f16x3,
+               x_planes, g_planes, grid, dwp, live=live)
         K.conv_unpack_grad(dwp, grads[wname], C, C)
 
     # final conv (s3d:391):  o = conv(relu(h)).  g_h as planes (the DFE dgrad and weight
@@ -665,7 +694,7 @@ def _split_backward(W, sv, gout, grads):
                         mask_planes=mask_planes, out_max=K.p(ghmax), out_planes=pg, planes_only=True,
                         colsum=grads["dfe_tail.bias"])
     dwp = torch.zeros((27, K.pad32(cin), C), dtype=torch.float32, device=dev)
-    K.conv3d_thin_wgrad_planes(sv["ph"], go, cin, gomax, 0, grid, dwp)
+    K.conv3d_thin_wgrad_planes(sv["ph"], go, cin, gomax, 0, grid, dwp, live=_live_frames(grid, pad, 0))
     K.conv_unpack_grad(dwp, grads["final_layer.layers.2.conv.weight"], cin, C)
     K.colsum(go, grads["final_layer.layers.2.conv.bias"], rows=rows, C=cin, ld=go.shape[-1])
     # DFE tail (s3d:356):  h = conv_d(relu(out_last)) + 2 s.  g_out as planes (the stage
@@ -679,7 +708,7 @@ def _split_backward(W, sv, gout, grads):
     _timed("conv_dgrad", flops, K.conv3d_f16x3, gh_pl, K.conv_pack_f16x3(P["dfe_tail.weight"], 1), grid,
            mask=mask, mask_planes=mask_planes, out_max=K.p(gom), out_planes=pg, planes_only=True,
            colsum=grads[W.stages[-1].pre + "swin_tail.bias"])
-    split_wgrad(sv["pout"], gh_pl, "dfe_tail.weight")
+    split_wgrad(sv["pout"], gh_pl, "dfe_tail.weight", live=_live_frames(grid, pad, 1))
     g_out = None                                   # fp32 g_out of an inner stage (None: planes only)
     for k in reversed(range(len(W.stages))):
         st, ss = W.stages[k], sv["stages"][k]
@@ -695,7 +724,9 @@ def _split_backward(W, sv, gout, grads):
         mask, mask_planes = _relu_mask(ss["a"], ss["planes"])
         g = [_timed("conv_dgrad", flops, K.conv3d_f16x3, gp, K.conv_pack_f16x3(P[pre + "swin_tail.weight"], 1),
                     grid, mask=mask, mask_planes=mask_planes)]
-        split_wgrad(ss["planes"], gp, pre + "swin_tail.weight")
+        # the last stage's g is the DFE input gradient's planes: two convs below the crop
+        split_wgrad(ss["planes"], gp, pre + "swin_tail.weight",
+                    live=_live_frames(grid, pad, 2) if gout_pl is not None else None)
         del gp
         d_tok, d_tok_t = _stage_swin_backward(W, st, ss, sv, g, grads)
         # embed (k4s4 conv) backward: dL/d in_k = (embed backward) + g_out_k (the ResSwin

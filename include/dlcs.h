@@ -467,6 +467,18 @@ size_t dlcs_conv3d_k3_wgrad_f16x3_workspace_bytes(int64_t B, int64_t D, int64_t 
 int dlcs_conv3d_k3_wgrad_f16x3(const void* xplanes, const void* gplanes, float* dw_packed, int64_t B, int64_t D,
                                int64_t H, int64_t W, void* workspace, size_t workspace_bytes,
                                dlcs_stream_t stream);
+/* The same with a live-frame window: the caller PROMISES that g is exactly zero (all 160
+ * channels) outside frames [t_lo, t_hi) of every batch item -- as behind the crop of a
+ * padded time axis, whose backward writes zero frames that each k3 input gradient widens
+ * by one per side.  The kernel's units of two frames that miss the window are neither
+ * read nor multiplied and the voxel ranges are cut over the live units, so g may hold
+ * anything there as far as this call goes -- but if it is not zero the result is not the
+ * weight gradient.  The window is clamped to [0, D); [0, D) gives the un-windowed call
+ * bit for bit, an empty window leaves dw_packed unchanged.  Same workspace.  Run-to-run
+ * deterministic; the partial sums differ from the un-windowed call's (other range cuts). */
+int dlcs_conv3d_k3_wgrad_f16x3_live(const void* xplanes, const void* gplanes, float* dw_packed, int64_t B, int64_t D,
+                                    int64_t H, int64_t W, int64_t t_lo, int64_t t_hi, void* workspace,
+                                    size_t workspace_bytes, dlcs_stream_t stream);
 /* fp32 thin-end Conv3d k3 (the ConvBlocks' 2E <-> 160 ends: SFE s3d:384, final
  * layer s3d:391; replaces their fp32 nn.Conv3d calls, swin3D.py:225-273) on fp16
  * matrix cores (conv3d_thin_f16x3.inc): the fp32 activation is read once and
@@ -522,6 +534,25 @@ int dlcs_conv3d_thin_wgrad_planes_f16x3(const void* bigplanes, const float* thin
                                         const unsigned* thin_max, int big_is_co, float* dw_packed, int64_t cout_pad,
                                         int64_t cin_pad, int64_t B, int64_t D, int64_t H, int64_t W, void* workspace,
                                         size_t workspace_bytes, dlcs_stream_t stream);
+/* Windowed forms, for a time axis whose pad frames are cropped after the final conv.
+ *   dlcs_conv3d_thin_out_planes_f16x3_slabs: only the 4-frame slabs [tb0, tb1) (clamped to
+ *     [0, D / 4)) of every batch item are computed; the output rows of the other slabs are
+ *     left untouched, so the caller must not read them.  [0, D / 4) = the call above.
+ *   dlcs_conv3d_thin_wgrad_planes_f16x3_live (big_is_co = 0 only; with big_is_co = 1 the
+ *     window must be [0, D)): the caller PROMISES that the thin tensor g is exactly zero
+ *     outside frames [t_lo, t_hi) of every batch item.  A patch reads g through a one-frame
+ *     tap halo, so the patches of slab t are skipped iff frames [4 t - 1, 4 t + 5) miss the
+ *     window; the workgroups' ranges are cut over the live patches.  [0, D) = the call above
+ *     bit for bit; an empty window leaves dw_packed unchanged.                  */
+int dlcs_conv3d_thin_out_planes_f16x3_slabs(const void* xplanes, const void* wthin, const float* bias, float* out,
+                                            int64_t cout, int64_t cout_ld, int64_t B, int64_t D, int64_t H, int64_t W,
+                                            int accumulate, int relu_out, int64_t tb0, int64_t tb1,
+                                            dlcs_stream_t stream);
+int dlcs_conv3d_thin_wgrad_planes_f16x3_live(const void* bigplanes, const float* thin, int64_t thin_ch,
+                                             int64_t thin_ld, const unsigned* thin_max, int big_is_co,
+                                             float* dw_packed, int64_t cout_pad, int64_t cin_pad, int64_t B, int64_t D,
+                                             int64_t H, int64_t W, int64_t t_lo, int64_t t_hi, void* workspace,
+                                             size_t workspace_bytes, dlcs_stream_t stream);
 /* grad [cout][cin][3][3][3] (+)= unpack(dw_packed)                           */
 int dlcs_conv3d_unpack_wgrad(const float* dw_packed, float* grad, int64_t cout, int64_t cin, int64_t cout_pad,
                              int64_t cin_pad, int accumulate, dlcs_stream_t stream);
